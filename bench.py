@@ -15,17 +15,23 @@ the reference's trained policy (average trajectory length 200/200, examples/cart
 cell 10); `value` counts LIVE environment steps only.
 
 Timing contract: W untimed warm-up steps, then a block of EXACTLY K steps bracketed by barrier +
-torch.cuda.synchronize() on both sides; that block is repeated `--reps` times from the same post-warm-up state
-(identical work every time), each repetition's time is the MAX over ranks, and `ms_per_step` / `value` come from
-the MEDIAN repetition (min / max are printed beside it).
+torch.cuda.synchronize() on both sides; by default that block runs once (K timed steps in all); `--reps R` repeats it
+R times from the same post-warm-up state (identical work every time), each repetition's time is the MAX over ranks,
+and `ms_per_step` / `value` come from the MEDIAN repetition (min / max are printed beside it).
+
+A plain run does only that and prints its line.  `--dump-outputs DIR` then writes what the last timed step computed
+(the state after it, its cost and done flag, every environment's termination step) as DIR/<name>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.  Everything else the
+bench measures -- `cpu_baseline`, the `secondary` block, `parity_evidence` and the per-kernel timings of the
+stepwise modes -- runs only with `--full`.
 
 Launching: `python bench.py --gpus N` starts N fresh rank processes itself (one per GPU, before anything in
 the parent touches the GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it uses the
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* of the launcher.  Rank 0 prints ONE JSON line.
 
-`roofline` is for the dominant hand-written kernel, timed live with HIP events on the launch stream;
-`cpu_baseline` is the CPU oracle (oracle/, the port of the reference's batch-1 loop) on this box's host cores
-over a bounded sample of the same workload; `secondary` carries the other BASELINE configs' closed loops, the
+`roofline` is for the dominant hand-written kernel, timed live with HIP events on the launch stream (the launches
+of the timed block itself); with `--full`, `cpu_baseline` is the CPU oracle (oracle/, the port of the reference's
+batch-1 loop) on the host cores of the machine it runs on over a bounded sample of the same workload; `secondary` carries the other BASELINE configs' closed loops, the
 HBM-bound entry points (buffers rotated through a pool larger than the 256 MB Infinity Cache) and the
 optimiser step, each measured in the same run.
 """
@@ -56,7 +62,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10, help="repetitions of the timed K-step block (median reported)")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the timed K-step block from the same post-warm-up state (median reported); "
+                    "1 = exactly --steps timed steps")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: the secondary measurements, the CPU "
+                    "baseline, the stepwise modes' per-kernel timings and the parity evidence (off: the run times only the headline's --steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32, rank 0's "
+                         "environments; a seeded sample of them when the arrays exceed 64 MB)")
     ap.add_argument("--batch", type=int, default=0, help="environments per GPU (weak) or in total (strong); 0 = the BASELINE size of --system")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch environments per GPU; strong: --batch environments in total, sharded contiguously over the ranks")
@@ -70,8 +82,8 @@ def parse():
                          "environment and rounded to two float16 pieces (22 bits), three piece products on the f16 matrix cores")
     ap.add_argument("--chunk", type=int, default=0, help="steps per persistent launch (0 = all K steps in one launch)")
     ap.add_argument("--prewarm", type=float, default=0.3, help="seconds of untimed clock pre-warm on scratch state before the W warm-up steps (0 for counter runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (other configs, HBM-bound entry points, optimiser step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements (other configs, HBM-bound entry points, optimiser step)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path on one GPU)")
     ap.add_argument("--torch-mlp", action="store_true", help="value gradient through PyTorch matmuls instead of the fused kernel")
     ap.add_argument("--stepwise", action="store_true", help="two launches per step (value_grad + vhjb_step) instead of the persistent rollout kernel")
@@ -188,6 +200,7 @@ class FusedLoop:
             self.x = out["x_out"]
             self.t += k
             left -= k
+            self.last = out
 
     def save(self):
         return self.x.clone(), self.done_step.clone(), self.t
@@ -197,8 +210,9 @@ class FusedLoop:
         self.done_step.copy_(st[1])
 
 
-def time_fused(wl, K, W, reps, chunk, barrier, prewarm=0.3):
-    """-> (per-rep wall seconds, per-launch (ms, steps) list, live env-steps of one K-step block on this rank)"""
+def time_fused(wl, K, W, reps, chunk, barrier, prewarm=0.3, last=None):
+    """-> (per-rep wall seconds, per-launch (ms, steps) list, live env-steps of one K-step block on this rank); `last` (a dict), when
+    given, receives the outputs of the last timed step"""
     loop = FusedLoop(wl, chunk)
     if prewarm:
         loop.prewarm(prewarm)
@@ -215,9 +229,38 @@ def time_fused(wl, K, W, reps, chunk, barrier, prewarm=0.3):
         barrier()
         walls.append(time.perf_counter() - t0)
         launches += [(a.elapsed_time(b), k) for a, b, k in evs]
+    if last is not None:
+        last.update(last_step_outputs(loop.x, loop.last["cost"][-1], loop.last["done"][-1], loop.done_step))
     ds = loop.done_step.long()
     live = int(torch.where(ds < 0, torch.full_like(ds, K), (ds - W).clamp(min=0, max=K)).sum().item())
     return walls, launches, live
+
+
+def last_step_outputs(x_next, cost, done, done_step):
+    """What a caller of the timed path holds after its last step, one row per environment: the state after the step (B, n), the
+    step's running cost and done flag (B,), and the termination step of every environment (B,; -1 = still running)."""
+    return dict(x_next=x_next.clone(), cost=cost.clone(), done=done.clone(), done_step=done_step.clone())
+
+
+DUMP_BYTES = 63 << 20      # the .npy files of --dump-outputs stay below 64 MB together (headers included)
+
+
+def dump_outputs(d, arrays, seed=0):
+    """Write `arrays` (device tensors, environments along the first axis) as d/<name>.npy in float32 (done_step's step indices are exact
+    there).  When they do not fit DUMP_BYTES, every array keeps the same seeded sample of environments, in index order, and
+    d/env_index.npy (float64) lists it."""
+    os.makedirs(d, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * int(np.prod(a.shape[1:])) for a in arrays.values())
+    idx = None
+    if B * row_bytes > DUMP_BYTES:
+        k = DUMP_BYTES // (row_bytes + 8)
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        np.save(os.path.join(d, "env_index.npy"), idx.numpy().astype(np.float64))
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(d, name + ".npy"), a.float().cpu().numpy())
 
 
 def rollout_traffic_model(n, m, B, steps_per_launch):
@@ -536,13 +579,17 @@ def main():
     n, m, ctl, dyn = wl["n"], wl["m"], wl["ctl"], wl["dyn"]
     fused = ctl.fused_value_grad and not args.stepwise
     kernel_ms = {}
+    last = {}
 
     if fused:
-        walls, launches, live = time_fused(wl, K, W, reps, args.chunk, barrier, prewarm=args.prewarm)
+        walls, launches, live = time_fused(wl, K, W, reps, args.chunk, barrier, prewarm=args.prewarm, last=last)
         roofline = mfma_roofline(wl, launches, B)
         kernel_ms["k_vhjb_rollout_mfma_ms_per_launch"] = roofline["avg_launch_ms"]
     else:
-        walls, live, roofline, kernel_ms = stepwise_loop(args, wl, K, W, reps, barrier)
+        walls, live, roofline, kernel_ms = stepwise_loop(args, wl, K, W, reps, barrier, last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
 
     walls_t = torch.tensor(walls, device="cuda", dtype=torch.float64)
     live_t = torch.tensor([live], device="cuda", dtype=torch.int64)
@@ -574,7 +621,7 @@ def main():
                            backend=(args.backend if world > 1 else None)),
                roofline=roofline, kernels=kernel_ms)
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = []
         if rank == 0 and world == 1 and fused:
             # the headline workload in the other (opt-in) arithmetics of the value network
@@ -638,8 +685,9 @@ def main():
             "bf16x3": "float32 operands split exactly into 3 bf16 pieces, 6 piece products on the bf16 MFMA, f32 accumulation",
             "f16x2": "float32 operands scaled per environment by a power of two and rounded to 2 f16 pieces (22 significant bits), 3 piece products "
                      "on the f16 MFMA, f32 accumulation; inputs, outputs, layer 1, dynamics and costs are float32"}[args.arithmetic]
-        out["parity_evidence"] = parity_evidence(args.arithmetic, args.system)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:     # the host-core baseline is reported at N = 1 only
+        if args.full:
+            out["parity_evidence"] = parity_evidence(args.arithmetic, args.system)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:     # the host-core baseline is reported at N = 1 only
         out["cpu_baseline"] = cpu_baseline(dyn, ctl, wl["x0"], args.cpu_sample_envs)
     if rank == 0:
         sys.stdout.flush()
@@ -649,8 +697,9 @@ def main():
         dist.destroy_process_group()
 
 
-def stepwise_loop(args, wl, K, W, reps, barrier):
-    """Diagnostic modes (--stepwise / --torch-mlp): one value-gradient launch + one step launch per environment step."""
+def stepwise_loop(args, wl, K, W, reps, barrier, last):
+    """Diagnostic modes (--stepwise / --torch-mlp): one value-gradient launch + one step launch per environment step.  `last` (a dict)
+    receives the outputs of the last timed step; the per-kernel timings and the roofline take runs of their own (--full only)."""
     from q_learning_with_hjb_amd import _ops
     ctl, dyn, n, B = wl["ctl"], wl["dyn"], wl["n"], wl["B"]
     sysh, task = dyn.system, ctl._task
@@ -681,6 +730,9 @@ def stepwise_loop(args, wl, K, W, reps, barrier):
         t_cur += K
     ds = done_step.long()
     live = int(torch.where(ds < 0, torch.full_like(ds, K), (ds - (t_cur - K)).clamp(min=0, max=K)).sum().item())
+    last.update(last_step_outputs(traj[t_cur % RING], cost[(t_cur - 1) % RING], done[(t_cur - 1) % RING], done_step))
+    if not args.full:
+        return walls, live, None, {}
 
     def timed_run(fn, reps_=100, warm=20):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

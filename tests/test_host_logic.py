@@ -346,6 +346,30 @@ def test_bench_self_launches_n_ranks():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_stay_under_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 .npy files, whole arrays while they fit the cap; beyond it every array keeps the SAME seeded
+    sample of environments (listed in env_index.npy), so two runs -- or two builds -- dump comparable files."""
+    import bench
+    B = 1 << 16
+    out = bench.last_step_outputs(torch.randn(B, 4), torch.arange(B).float(), torch.zeros(B), torch.arange(B, dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "whole"), out)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["cost.npy", "done.npy", "done_step.npy", "x_next.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "x_next.npy"), out["x_next"].numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)                 # B x 28 bytes no longer fit
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["cost.npy", "done.npy", "done_step.npy", "env_index.npy", "x_next.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= (1 << 20) + 1024 * len(files)   # (+ the .npy headers)
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert 0 < idx.size < B and np.all(np.diff(idx) > 0)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "done_step.npy"), idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x_next.npy"), out["x_next"].numpy()[idx.astype(np.int64)])
+
+
 def test_oracle_passes_address_and_ub_sanitizers():
     """SURVEY section 5 (race / memory checking): the restatement the GPU kernels are judged against is itself run under
     AddressSanitizer + UBSan (`make -C oracle asan`: every batch entry point, both precisions, all five systems, ragged batch,

@@ -7,7 +7,7 @@ OUT=gpurun_out/prof_r02
 mkdir -p $OUT
 R="rocprofv3 --output-format csv"
 # 1. kernel trace + stats of the bench command itself (default arithmetic = f16x2; its secondary block runs the bf16x3 and f32 kernels too)
-$R --kernel-trace --stats -d $OUT/trace -- python3 bench.py > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
+$R --kernel-trace --stats -d $OUT/trace -- python3 bench.py --full --reps 10 > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
 # 2. HBM traffic of the rollout kernel at two launch lengths (every launch of a run has the same length: warm-up = K, no pre-warm)
 for K in 100 20; do
   for C in FETCH_SIZE WRITE_SIZE; do

@@ -10,7 +10,7 @@ mkdir -p $OUT
 R="timeout -k 10 400 rocprofv3 --output-format csv"   # (a profiled run that aborts can hang in the profiler's signal handler: bounded)
 if [ $STAGE != B ]; then
 # 1. kernel trace + stats of the bench command itself (default arithmetic = float32 MFMA; its secondary block runs the opt-in kernels too)
-$R --kernel-trace --stats -d $OUT/trace -- python3 bench.py > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
+$R --kernel-trace --stats -d $OUT/trace -- python3 bench.py --full --reps 10 > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
 # 2. HBM traffic of the rollout kernel at two launch lengths (every launch of a run has the same length: warm-up = K, no pre-warm)
 for K in 100 20; do
   for C in FETCH_SIZE WRITE_SIZE; do
@@ -21,7 +21,7 @@ done
 $R --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/sq_f32/a -- python3 bench.py --no-secondary --no-cpu-baseline --prewarm 0 --steps 100 --warmup 100 --reps 3 > $OUT/sq_f32_a.json 2> $OUT/sq_f32_a.err || exit 1
 $R --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY -d $OUT/sq_f32/b -- python3 bench.py --no-secondary --no-cpu-baseline --prewarm 0 --steps 100 --warmup 100 --reps 3 > $OUT/sq_f32_b.json 2> $OUT/sq_f32_b.err || exit 1
 # 7. the plain bench line (no profiler attached)
-python3 bench.py > $OUT/r03_bench_builder_run.json 2> $OUT/bench_builder_run.err || exit 1
+python3 bench.py --full --reps 10 > $OUT/r03_bench_builder_run.json 2> $OUT/bench_builder_run.err || exit 1
 fi
 if [ $STAGE != A ]; then
 # 4. the parameter gradient: durations of its three implementations, HBM bytes and matrix-pipe occupancy of the cooperative kernel
