@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define HJBX_VERSION 111 /* major*100 + minor */
+#define HJBX_VERSION 112 /* major*100 + minor */
 #define HJBX_MAX_N 10    /* largest state dimension (NearHoverQuadcopter) */
 #define HJBX_MAX_M 3     /* largest control dimension */
 
@@ -190,6 +190,26 @@ typedef struct hjbx_mlp {
     double eps_scalar;       /* epsilon_scalar */
 } hjbx_mlp;
 
+/* Soft-PD value network of the notebooks (SoftPDValueApproximator: examples/cartpole_balancing.ipynb cell 6, drone_hovering.ipynb cell 6,
+ * double_integrator_optimal_time.ipynb cell 5, 10D_quadcopte.ipynb cell 6): Dense layers WITH biases and a scalar output,
+ *   h1 = act(z W1 + b1), h2 = act(h1 W2 + b2), h3 = act(h2 W3 + b3), V = h3 . w4 + b4,   z = (wrap(x - xf) - mean) / std
+ * (no eps |e|^2 term; positivity is only encouraged by the training loss).  Device pointers, Flax Dense layout (in, out) row-major. */
+typedef struct hjbx_softpd_mlp {
+    const void* W1; /* (n,  h1) */
+    const void* b1; /* (h1) */
+    const void* W2; /* (h1, h2) */
+    const void* b2; /* (h2) */
+    const void* W3; /* (h2, h3) */
+    const void* b3; /* (h3) */
+    const void* w4; /* (h3, 1) */
+    const void* b4; /* (1) */
+    int32_t h1, h2, h3;
+    int32_t activation;      /* hjbx_activation, applied after each of the three hidden layers */
+    double mean[HJBX_MAX_N]; /* normalization_mean */
+    double std[HJBX_MAX_N];  /* normalization_std  */
+    double xf[HJBX_MAX_N];
+} hjbx_softpd_mlp;
+
 /* ---- library / handles --------------------------------------------------------------------- */
 int hjbx_version(void);
 /* Copies the calling thread's last error message (NUL terminated) into buf; returns its length. */
@@ -325,6 +345,17 @@ int hjbx_vhjb_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const h
                           int n_steps, int T_max, const float* x, float* traj, float* u_log, float* cost, float* done,
                           float* resid, int32_t* done_step, float* x_out, const int32_t* env_order, int64_t B, void* workspace,
                           void* stream);
+
+/* The soft-PD network (hjbx_softpd_mlp) in the two fused kernels above: V (B,) and gradV (B,n) as hjbx_value_grad_f32 (V or gradV may be NULL),
+ * and the closed loop with exactly the arguments, chunking (t_first, n_steps), in-place done_step, logs, x_out, env_order and rollout
+ * workspace of hjbx_vhjb_rollout_f32 (bit-identical to hjbx_softpd_value_grad_f32 + hjbx_vhjb_step_f32 per step).  Always the float32 MFMA
+ * arithmetic: HJBX_OPT_MLP_ARITHMETIC does not apply.  Features [128,128,64] and the built-in systems only (HJBX_EUNSUPPORTED otherwise,
+ * user-defined systems included).  There is no fused parameter gradient for this network: it is trained through autograd. */
+int hjbx_softpd_value_grad_f32(const hjbx_system* sys, const hjbx_softpd_mlp* mlp, const float* x, float* V, float* gradV, int64_t B,
+                               void* stream);
+int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const hjbx_softpd_mlp* mlp, int integrator, int t_first,
+                            int n_steps, int T_max, const float* x, float* traj, float* u_log, float* cost, float* done, float* resid,
+                            int32_t* done_step, float* x_out, const int32_t* env_order, int64_t B, void* workspace, void* stream);
 
 /* The parameter gradient of one value-learning step (vhjb.py:227-253 and the jax.grad calls of :282-284) for a minibatch of B samples
  * (x (B,n), cost (B,), done (B,) as 0/1 floats), fused on the matrix cores:

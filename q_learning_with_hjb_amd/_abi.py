@@ -41,9 +41,12 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_train.hip", ("-fno-slp-vectorize",), "hjbx_train.o"),
           ("hjbx_train_coop.hip", ("-fno-slp-vectorize",), "hjbx_train_coop.o"),
           ("hjbx_fit.hip", (), "hjbx_fit.o"),
+          ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=0",), "hjbx_softpd_relu.o"),    # soft-PD network: once per activation, like hjbx_mlp.hip
+          ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=1",), "hjbx_softpd_tanh.o"),
+          ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=2",), "hjbx_softpd_sin.o"),
           ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds three headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
-_HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
+_HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
             "hjbx_user_kernels.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
@@ -108,6 +111,27 @@ class HjbxMlp(C.Structure):
         ("std", C.c_double * HJBX_MAX_N),
         ("xf", C.c_double * HJBX_MAX_N),
         ("eps_scalar", C.c_double),
+    ]
+
+
+class HjbxSoftpdMlp(C.Structure):
+    """struct hjbx_softpd_mlp"""
+    _fields_ = [
+        ("W1", C.c_void_p),
+        ("b1", C.c_void_p),
+        ("W2", C.c_void_p),
+        ("b2", C.c_void_p),
+        ("W3", C.c_void_p),
+        ("b3", C.c_void_p),
+        ("w4", C.c_void_p),
+        ("b4", C.c_void_p),
+        ("h1", C.c_int32),
+        ("h2", C.c_int32),
+        ("h3", C.c_int32),
+        ("activation", C.c_int32),
+        ("mean", C.c_double * HJBX_MAX_N),
+        ("std", C.c_double * HJBX_MAX_N),
+        ("xf", C.c_double * HJBX_MAX_N),
     ]
 
 
@@ -220,7 +244,7 @@ EXPORTED_SYMBOLS = (
      "hjbx_last_compile_log", "hjbx_system_destroy", "hjbx_dims",
      "hjbx_reduce_workspace_bytes", "hjbx_rollout_workspace_bytes", "hjbx_value_grad_f32", "hjbx_vhjb_rollout_f32",
      "hjbx_value_loss_grad_workspace_bytes", "hjbx_value_loss_grad_f32", "hjbx_mix_gradients_f32", "hjbx_mix_adam_f32", "hjbx_replay_gather_f32",
-     "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32"]
+     "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32", "hjbx_softpd_value_grad_f32", "hjbx_softpd_rollout_f32"]
     + [f"hjbx_{k}_{s}" for k in _typed_signatures() for s in ("f32", "f64")]
 )
 
@@ -264,6 +288,10 @@ def lib() -> C.CDLL:
         L.hjbx_value_grad_f32.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _VP]
         L.hjbx_vhjb_rollout_f32.restype = C.c_int
         L.hjbx_vhjb_rollout_f32.argtypes = [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]
+        L.hjbx_softpd_value_grad_f32.restype = C.c_int
+        L.hjbx_softpd_value_grad_f32.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _VP]
+        L.hjbx_softpd_rollout_f32.restype = C.c_int
+        L.hjbx_softpd_rollout_f32.argtypes = L.hjbx_vhjb_rollout_f32.argtypes
         L.hjbx_value_loss_grad_workspace_bytes.restype = C.c_size_t
         L.hjbx_value_loss_grad_workspace_bytes.argtypes = [_I64]
         L.hjbx_value_loss_grad_f32.restype = C.c_int

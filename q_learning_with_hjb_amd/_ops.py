@@ -232,6 +232,16 @@ def value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
     return V, g
 
 
+def softpd_value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
+    """value_grad for the soft-PD network (mlp_desc: _abi.HjbxSoftpdMlp): hjbx_softpd_value_grad_f32."""
+    B = x.shape[0]
+    _chk(x, "x", (B, sys.n), torch.float32)
+    V = torch.empty((B,), dtype=x.dtype, device=x.device) if want_v else None
+    g = torch.empty_like(x) if want_grad else None
+    check(lib().hjbx_softpd_value_grad_f32(sys.ptr, ref(mlp_desc), _p(x), _p(V), _p(g), B, _stream()))
+    return V, g
+
+
 def vhjb_rollout(sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first=0, integrator=_abi.EULER, log_traj=True, log_u=False,
                  log_residual=False, want_x_out=False, env_order=None, out=None):
     """`n_steps` closed-loop VHJB steps (value gradient + step) in ONE kernel launch (f32).  `done_step` (B,) int32 is
@@ -240,6 +250,19 @@ def vhjb_rollout(sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first=0, i
     `env_order` (B,) int32: permutation packing the environments into the kernel's tiles (live ones first = compaction).
     `out`: dict of preallocated contiguous slabs to write into (keys traj / u / cost / done / residual, e.g. time slices of a
     whole-horizon log) instead of fresh tensors."""
+    return _mfma_rollout(lib().hjbx_vhjb_rollout_f32, sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first, integrator, log_traj, log_u,
+                         log_residual, want_x_out, env_order, out)
+
+
+def softpd_rollout(sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first=0, integrator=_abi.EULER, log_traj=True, log_u=False,
+                   log_residual=False, want_x_out=False, env_order=None, out=None):
+    """vhjb_rollout for the soft-PD network (mlp_desc: _abi.HjbxSoftpdMlp): hjbx_softpd_rollout_f32, same arguments and results."""
+    return _mfma_rollout(lib().hjbx_softpd_rollout_f32, sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first, integrator, log_traj, log_u,
+                         log_residual, want_x_out, env_order, out)
+
+
+def _mfma_rollout(entry, sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first, integrator, log_traj, log_u, log_residual, want_x_out,
+                  env_order, out):
     B = x.shape[0]
     _chk(x, "x", (B, sys.n), torch.float32)
     _chk(done_step, "done_step", (B,), torch.int32)
@@ -261,9 +284,8 @@ def vhjb_rollout(sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first=0, i
     x_out = torch.empty_like(x) if want_x_out else None
     if env_order is not None:
         _chk(env_order, "env_order", (B,), torch.int32)
-    check(lib().hjbx_vhjb_rollout_f32(sys.ptr, ref(task), ref(mlp_desc), int(integrator), int(t_first), int(n_steps), int(T_max), _p(x),
-                                      _p(traj), _p(ulog), _p(cost), _p(done), _p(resid), _p(done_step), _p(x_out), _p(env_order), B,
-                                      _p(_rollout_workspace(dev)), _stream()))
+    check(entry(sys.ptr, ref(task), ref(mlp_desc), int(integrator), int(t_first), int(n_steps), int(T_max), _p(x), _p(traj), _p(ulog), _p(cost),
+                _p(done), _p(resid), _p(done_step), _p(x_out), _p(env_order), B, _p(_rollout_workspace(dev)), _stream()))
     return dict(traj=traj, u=ulog, cost=cost, done=done, residual=resid, x_out=x_out)
 
 

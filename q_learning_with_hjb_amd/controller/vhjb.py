@@ -152,6 +152,97 @@ class ValueFunctionApproximator(torch.nn.Module):
         return _ops.value_grad(self.dynamics.system, self.descriptor(), x, want_v, want_grad)
 
 
+class SoftPDValueFunctionApproximator(torch.nn.Module):
+    """The notebooks' second value network (SoftPDValueApproximator: examples/cartpole_balancing.ipynb cell 6, drone_hovering.ipynb cell 6,
+    double_integrator_optimal_time.ipynb cell 5, 10D_quadcopte.ipynb cell 6): Dense layers WITH biases and a scalar output,
+        h1 = act(z W1 + b1), h2 = act(h1 W2 + b2), h3 = act(h2 W3 + b3), V = h3 w4 + b4,   z = (e - mean)/std, e = wrap(x - xf).
+    Nothing makes V positive definite: the training loss pushes V(x) >= V(xf) (VHJBController soft_pd_regularization) and can start with a
+    warm-up fit to e'Pe (soft_pd_warmup_epochs).  Flax Dense init: kernels lecun_normal, biases zero.  Parameters, in order:
+    W1 (n, h1), b1, W2 (h1, h2), b2, W3 (h2, h3), b3, w4 (h3, 1), b4 (1,).  The fused kernels (hjbx_softpd_value_grad_f32 /
+    hjbx_softpd_rollout_f32) run it in float32 for relu, tanh and sin."""
+
+    FUSED_ACTIVATIONS = ValueFunctionApproximator.FUSED_ACTIVATIONS
+    _ACT = ValueFunctionApproximator._ACT
+
+    def __init__(self, dynamics: Dynamics, features: Sequence[int], mean, std, xf, using_batch_norm: bool = False, dtype=torch.float32,
+                 device=None, generator=None, activation: str = "relu"):
+        super().__init__()
+        if activation not in self._ACT:
+            raise ValueError(f"activation must be one of {sorted(self._ACT)}, got {activation!r}")
+        self.activation = activation
+        if using_batch_norm:
+            raise NotImplementedError("BatchNorm is disabled in every reference config and is not implemented")
+        if len(features) != 3:
+            raise NotImplementedError("the fused kernel and this module take exactly three hidden Dense layers")
+        self.dynamics = dynamics
+        self.features = tuple(int(f) for f in features)
+        n = dynamics.state_dim
+        dims = (n,) + self.features + (1,)
+        self.layers = torch.nn.ParameterList()
+        for i in range(4):
+            w = torch.empty((dims[i], dims[i + 1]), dtype=dtype, device=device)
+            self.layers.append(torch.nn.Parameter(lecun_normal_(w, generator)))
+            self.layers.append(torch.nn.Parameter(torch.zeros((dims[i + 1],), dtype=dtype, device=device)))
+        self.register_buffer("mean", torch.as_tensor(np.asarray(mean, np.float64), dtype=dtype, device=device))
+        self.register_buffer("std", torch.as_tensor(np.asarray(std, np.float64), dtype=dtype, device=device))
+        self.register_buffer("xf", torch.as_tensor(np.asarray(xf, np.float64), dtype=dtype, device=device))
+        self._np = dict(mean=np.asarray(mean, np.float64), std=np.asarray(std, np.float64), xf=np.asarray(xf, np.float64))
+
+    def error_coords(self, x: torch.Tensor) -> torch.Tensor:
+        with torch.no_grad():
+            return _ops.wrap(self.dynamics.system, (x - self.xf).contiguous())
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        V, _ = self.value_and_grad(x, want_grad=False)
+        return V
+
+    def value_and_grad(self, x: torch.Tensor, want_grad: bool = True, weights=None):
+        """V (B,) and dV/dx (B, n), differentiable in the eight parameters (`weights`: stand-ins for them, in parameter order)."""
+        return self.value_and_grad_error(self.error_coords(x), want_grad, weights)
+
+    def value_and_grad_error(self, e: torch.Tensor, want_grad: bool = True, weights=None):
+        """value_and_grad at given error coordinates e = wrap(x - xf) (B, n).  The input gradient is reverse mode written out by hand from
+        dV/da3 = w4 . act'(a3): a plain first-order autograd graph in the parameters, as for the PD network."""
+        W1, b1, W2, b2, W3, b3, w4, b4 = self.layers if weights is None else weights
+        z = (e - self.mean) / self.std
+        act, dact = self._ACT[self.activation]
+        a1 = z @ W1 + b1
+        h1 = act(a1)
+        a2 = h1 @ W2 + b2
+        h2 = act(a2)
+        a3 = h2 @ W3 + b3
+        V = (act(a3) @ w4)[:, 0] + b4
+        if not want_grad:
+            return V, None
+        d3 = w4[:, 0] * dact(a3)
+        d2 = (d3 @ W3.t()) * dact(a2)
+        d1 = (d2 @ W2.t()) * dact(a1)
+        return V, (d1 @ W1.t()) / self.std
+
+    def value_at_target(self, weights=None) -> torch.Tensor:
+        """V(xf) as a 0-dim tensor, differentiable in the parameters (e = wrap(0) = 0: no kernel involved)."""
+        e = torch.zeros((1, self.dynamics.state_dim), dtype=self.mean.dtype, device=self.mean.device)
+        return self.value_and_grad_error(e, want_grad=False, weights=weights)[0][0]
+
+    def descriptor(self) -> _abi.HjbxSoftpdMlp:
+        d = _abi.HjbxSoftpdMlp()
+        for name, p in zip(("W1", "b1", "W2", "b2", "W3", "b3", "w4", "b4"), self.layers):
+            setattr(d, name, p.data_ptr())
+        d.h1, d.h2, d.h3 = self.features
+        d.activation = {"relu": _abi.ACT_RELU, "tanh": _abi.ACT_TANH, "sin": _abi.ACT_SIN}[self.activation]
+        _abi._fill(d.mean, self._np["mean"])
+        _abi._fill(d.std, self._np["std"])
+        _abi._fill(d.xf, self._np["xf"])
+        return d
+
+    @torch.no_grad()
+    def fused_value_grad(self, x: torch.Tensor, want_v=True, want_grad=True):
+        """Inference-only V and dV/dx from the fused MFMA kernel (float32)."""
+        for w in self.layers:
+            assert w.is_contiguous() and w.dtype == torch.float32
+        return _ops.softpd_value_grad(self.dynamics.system, self.descriptor(), x, want_v, want_grad)
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd bridges to the residual kernels (forward value + analytic first derivative)
 # ------------------------------------------------------------------------------------------------
@@ -257,8 +348,18 @@ class VHJBController(Controller):
 
     def __init__(self, dynamics: Dynamics, config, device=None, dtype=torch.float32, process_group=None,
                  residual_mode=_abi.RESIDUAL_NORMALISED, fused_value_grad: Optional[bool] = None,
-                 graph_updates: Optional[bool] = None, activation: str = "relu", fused_param_grad: Optional[bool] = None) -> None:
+                 graph_updates: Optional[bool] = None, activation: str = "relu", fused_param_grad: Optional[bool] = None,
+                 value_structure: str = "pd", soft_pd_regularization: float = 1.0, soft_pd_warmup_epochs: int = 0) -> None:
         super().__init__()
+        # value_structure: "pd" = ValueFunctionApproximator (controller/vhjb.py); "soft_pd" = SoftPDValueFunctionApproximator, trained with
+        # the hinge soft_pd_regularization * mean(relu(V(xf) - V(x))) on top of the HJB loss, after soft_pd_warmup_epochs epochs of fitting
+        # |V(x) - e'Pe| (examples/cartpole_balancing.ipynb cell 11)
+        if value_structure not in ("pd", "soft_pd"):
+            raise ValueError(f"value_structure must be 'pd' or 'soft_pd', got {value_structure!r}")
+        self.value_structure = value_structure
+        self.soft_pd_regularization = float(soft_pd_regularization)
+        self.soft_pd_warmup_epochs = int(soft_pd_warmup_epochs)
+        self.soft_pd_warmup = False           # True while train() is in a warm-up epoch: params_update fits e'Pe
         self.device = torch.device(device) if device is not None else _ops.require_device()
         self.dtype = dtype
         self.process_group = process_group
@@ -289,9 +390,17 @@ class VHJBController(Controller):
         self._task = _abi.make_task(self.state_dim, self.control_dim, self.Q, self.R, self.P, self.xf, self.uf, self.obs_min,
                                     self.obs_max, self.epsilon, Rinv=self.R_inv)
 
-        self.value_function_approximator = ValueFunctionApproximator(
-            dynamics, config.features, config.normalization_mean, config.normalization_std, self.xf, config.epsilon_scalar,
-            config.using_batch_norm, dtype=dtype, device=self.device, generator=self._init_gen, activation=activation)
+        soft = value_structure == "soft_pd"
+        if soft and self._distributed():
+            raise NotImplementedError("the soft-PD value network has no data-parallel update")
+        if soft:
+            self.value_function_approximator = SoftPDValueFunctionApproximator(
+                dynamics, config.features, config.normalization_mean, config.normalization_std, self.xf, config.using_batch_norm, dtype=dtype,
+                device=self.device, generator=self._init_gen, activation=activation)
+        else:
+            self.value_function_approximator = ValueFunctionApproximator(
+                dynamics, config.features, config.normalization_mean, config.normalization_std, self.xf, config.epsilon_scalar,
+                config.using_batch_norm, dtype=dtype, device=self.device, generator=self._init_gen, activation=activation)
         # activation: "relu" = controller/vhjb.py; "tanh" / "sin" = the notebooks' networks
         # the matrix-core kernels carry the five built-in systems; a user-defined system (Dynamics.device_source) runs the value network
         # through PyTorch and its own run-time compiled step / residual kernels
@@ -304,10 +413,12 @@ class VHJBController(Controller):
         # residuals and the second-order reverse sweep in closed form) for the float32 ReLU network of controller/vhjb.py, the tanh network
         # of examples/cartpole_balancing.ipynb and (state dimension <= 4) the sin network of examples/double_integrator_optimal_time.ipynb;
         # anything else (float64, HJBX_FUSED_PARAM_GRAD=0) goes through PyTorch autograd
-        can_fuse_pg = (dtype == torch.float32 and (activation in ("relu", "tanh") or (activation == "sin" and self.state_dim <= 4))
+        can_fuse_pg = (not soft and dtype == torch.float32 and (activation in ("relu", "tanh") or (activation == "sin" and self.state_dim <= 4))
                        and tuple(config.features) == (128, 128, 64) and self.device.type == "cuda" and not config.using_batch_norm and builtin)
         if fused_param_grad is None:
             fused_param_grad = can_fuse_pg and os.environ.get("HJBX_FUSED_PARAM_GRAD", "1") != "0"
+        if fused_param_grad and soft:
+            raise NotImplementedError("there is no fused parameter-gradient kernel for the soft-PD value network (it trains through autograd)")
         if fused_param_grad and not can_fuse_pg:
             raise NotImplementedError("the fused parameter-gradient kernels exist for float32 ReLU / tanh / sin (n <= 4) networks with features "
                                       "[128, 128, 64] on the built-in systems only")
@@ -433,10 +544,11 @@ class VHJBController(Controller):
         if self.fused_value_grad and self.dtype == torch.float32:
             done_step = torch.full((B,), -1, dtype=torch.int32, device=self.device)
             desc = self.value_function_approximator.descriptor()
+            fused_rollout = _ops.softpd_rollout if self.value_structure == "soft_pd" else _ops.vhjb_rollout
             chunk = self.compaction_interval if (self.compaction_interval and B >= self.compaction_min_batch) else 0
             if not chunk or chunk >= T + 1:
                 # the whole loop (T live steps + the forced terminal iteration) in one persistent kernel launch
-                out = _ops.vhjb_rollout(sysh, task, desc, x0, T + 1, T, done_step, integrator=integ,
+                out = fused_rollout(sysh, task, desc, x0, T + 1, T, done_step, integrator=integ,
                                         log_traj=True, log_u=log_u, log_residual=log_residual)
                 return dict(traj=out["traj"][:T + 1], cost=out["cost"], done=out["done"], done_step=done_step,
                             u=None if out["u"] is None else out["u"][:T], residual=out["residual"])
@@ -457,7 +569,7 @@ class VHJBController(Controller):
                     slabs["u"] = ulog[t0:t0 + k]
                 if log_residual:
                     slabs["residual"] = resid[t0:t0 + k]
-                _ops.vhjb_rollout(sysh, task, desc, x_cur, k, T, done_step, t_first=t0, integrator=integ, log_traj=True, log_u=log_u,
+                fused_rollout(sysh, task, desc, x_cur, k, T, done_step, t_first=t0, integrator=integ, log_traj=True, log_u=log_u,
                                   log_residual=log_residual, env_order=order, out=slabs)
                 t0 += k
                 x_cur = traj[t0]
@@ -609,6 +721,8 @@ class VHJBController(Controller):
             # step runs on, so a hipGraph capture cannot be joined to the stream of an older, still-alive autograd graph of the
             # same parameters (that unjoined cross-stream wait crashes hipStreamEndCapture)
             params = [p.detach().requires_grad_(True) for p in model_params]
+            if self.value_structure == "soft_pd":
+                return self._soft_pd_update(params, model_params, xs, dones, costs, regularization)
             V, g = self.value_function_approximator.value_and_grad(xs, weights=params)
             h_sum, h_sums = _HJBResidualSum.apply(g, xs, dones, self.dynamics.system, self._task, self.residual_mode)
             t_sum, _ = _TerminationResidualSum.apply(V, costs, dones, self.epsilon)
@@ -630,6 +744,34 @@ class VHJBController(Controller):
         self.optimizer.step()
         return hjb_loss + regularization * termination_loss, hjb_loss, termination_loss
 
+    def soft_pd_losses(self, xs, dones, costs, regularization, weights=None):
+        """The soft-PD network's losses at one minibatch (examples/cartpole_balancing.ipynb cell 11) as differentiable functions of `weights`
+        (stand-ins for the eight parameters; None = the parameters) -> (total, hjb, termination).
+        Warm-up (self.soft_pd_warmup): total = mean |V(x) - e'Pe| with P the CARE solution; hjb = termination = 0.
+        Main phase: the PD path's HJB term (same residual kernel, residual_mode and normaliser) + regularization * termination term
+        + soft_pd_regularization * mean(relu(V(xf) - V(x))), V(xf) part of the graph; hjb and termination are the two PD terms."""
+        vfa = self.value_function_approximator
+        if self.soft_pd_warmup:
+            V, _ = vfa.value_and_grad(xs, want_grad=False, weights=weights)
+            fit = (V - _ops.termination_cost(self.dynamics.system, self._task, xs)).abs().mean()
+            zero = torch.zeros((), dtype=fit.dtype, device=fit.device)
+            return fit, zero, zero
+        V, g = vfa.value_and_grad(xs, weights=weights)
+        h_sum, h_sums = _HJBResidualSum.apply(g, xs, dones, self.dynamics.system, self._task, self.residual_mode)
+        t_sum, _ = _TerminationResidualSum.apply(V, costs, dones, self.epsilon)
+        hjb_t = h_sum / (h_sums[1] + self.epsilon)
+        term_t = t_sum / (h_sums[2] + self.epsilon)
+        hinge = torch.relu(vfa.value_at_target(weights) - V).mean()
+        return hjb_t + regularization * term_t + self.soft_pd_regularization * hinge, hjb_t, term_t
+
+    def _soft_pd_update(self, params, model_params, xs, dones, costs, regularization):
+        total, hjb_t, term_t = self.soft_pd_losses(xs, dones, costs, regularization, weights=params)
+        grads = torch.autograd.grad(total, params, allow_unused=True)
+        for p, gr in zip(model_params, grads):
+            p.grad = torch.zeros_like(p) if gr is None else gr
+        self.optimizer.step()
+        return total.detach(), hjb_t.detach(), term_t.detach()
+
     def params_update_graphed(self, xs, dones, costs, regularization):
         """`params_update` replayed from a hipGraph captured on first use for this minibatch shape: the same kernels in the
         same order, without ~100 host-side launches per step.  The returned losses are views of the graph's static outputs:
@@ -641,9 +783,12 @@ class VHJBController(Controller):
         if float(regularization) != self._reg_val:          # (one launch saved whenever the weight did not move)
             self._reg_buf.fill_(float(regularization))
             self._reg_val = float(regularization)
-        if self._graphed_update is None or not self._graphed_update.matches(xs, dones, costs, self._reg_buf):
+        # (the soft-PD warm-up and main phase are different computations: one captured step each)
+        if (self._graphed_update is None or not self._graphed_update.matches(xs, dones, costs, self._reg_buf)
+                or getattr(self._graphed_update, "soft_pd_warmup", False) != self.soft_pd_warmup):
             self._graphed_update = GraphedStep(self.optimizer, list(self.value_function_approximator.parameters()), self._update_core,
                                                (xs, dones, costs, self._reg_buf))
+            self._graphed_update.soft_pd_warmup = self.soft_pd_warmup
         return self._graphed_update(xs, dones, costs, self._reg_buf)
 
     # -- the fit phase of one epoch, driven from the device ------------------------------------------------
@@ -689,6 +834,7 @@ class VHJBController(Controller):
         per_rank_batch = max(1, self.batch_size // self.world_size)
         for epoch in range(self.epochs):
             self.train_mode = False
+            self.soft_pd_warmup = self.value_structure == "soft_pd" and epoch < self.soft_pd_warmup_epochs
             ntraj = self.num_of_trajectories_per_epoch
             if ntraj > 0:
                 x0 = self._dev(self.dynamics.get_initial_state(batch_size=ntraj))
@@ -740,6 +886,7 @@ class VHJBController(Controller):
                     print(f"epoch:{epoch+1}, total loss:{average_total_loss_list[-1]:.5f}, regulation: {self.regularization:.1e},"
                           f"hjb loss:{average_hjb_loss_list[-1]:.5f}, termination loss:{average_termination_loss_list[-1]:.5f}")
 
+        self.soft_pd_warmup = False
         return (average_trajectory_cost_list, std_trajectory_cost_list, average_trajectory_length_list,
                 average_total_loss_list, average_hjb_loss_list, average_termination_loss_list)
 

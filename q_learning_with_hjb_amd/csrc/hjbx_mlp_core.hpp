@@ -183,6 +183,17 @@ template <int N> struct MlpLds {
     int next;                                // next unclaimed tile group of this workgroup's range
 };
 
+// Soft-PD head (examples/cartpole_balancing.ipynb cell 6, SoftPDValueApproximator): the biases of the three hidden layers and the
+// scalar output layer, staged in LDS next to the weights (385 floats).  Hidden feature f of a lane half h sits at accumulator register
+// s with f = 32 o + perm(s) + 4h: registers 4q .. 4q + 3 of block o are the four consecutive features 32 o + 8q + 4h + 0..3, one float4.
+struct MlpBias {
+    float b1[kH1], b2[kH2], b3[kH3], w4[kH3];
+    float b4;
+};
+template <int N> struct MlpLdsSoft : MlpLds<N> {
+    alignas(16) MlpBias bias;
+};
+
 template <int TL, int NOUT> __device__ __forceinline__ void zero_acc(f32x16 (&a)[TL][NOUT]) {
 #pragma unroll
     for (int t = 0; t < TL; ++t)
@@ -190,6 +201,20 @@ template <int TL, int NOUT> __device__ __forceinline__ void zero_acc(f32x16 (&a)
         for (int o = 0; o < NOUT; ++o)
 #pragma unroll
             for (int r = 0; r < 16; ++r) a[t][o][r] = 0.f;
+}
+
+// accumulators initialised with a bias vector instead of zeros (soft-PD head): the chain then adds the products to it
+template <int TL, int NOUT> __device__ __forceinline__ void bias_acc(f32x16 (&a)[TL][NOUT], const float* b, int h) {
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *reinterpret_cast<const float4*>(b + 32 * o + 8 * q + 4 * h);
+#pragma unroll
+            for (int t = 0; t < TL; ++t) {
+                a[t][o][4 * q] = v.x; a[t][o][4 * q + 1] = v.y; a[t][o][4 * q + 2] = v.z; a[t][o][4 * q + 3] = v.w;
+            }
+        }
 }
 
 // lane-dependent LDS operand bases of one wave; everything else is a compile-time offset
@@ -212,6 +237,15 @@ __device__ __forceinline__ void mlp_fill_lds(MlpLds<N>& L, const float* __restri
     for (int idx = tid; idx < kH2 * kH3; idx += THREADS) L.W3[(idx / kH3) * kLD3 + (idx % kH3)] = W3g[idx];
 }
 
+template <int THREADS>
+__device__ __forceinline__ void mlp_fill_bias(MlpBias& L, const float* __restrict__ b1g, const float* __restrict__ b2g, const float* __restrict__ b3g,
+                                              const float* __restrict__ w4g, const float* __restrict__ b4g, int tid) {
+    for (int idx = tid; idx < kH1; idx += THREADS) L.b1[idx] = b1g[idx];
+    for (int idx = tid; idx < kH2; idx += THREADS) L.b2[idx] = b2g[idx];
+    for (int idx = tid; idx < kH3; idx += THREADS) { L.b3[idx] = b3g[idx]; L.w4[idx] = w4g[idx]; }
+    if (tid == 0) L.b4 = b4g[0];
+}
+
 template <int N> __device__ __forceinline__ MlpCtx mlp_ctx(MlpLds<N>& L, int lane) {
     constexpr int NP = MlpLds<N>::NP;
     MlpCtx c;
@@ -230,9 +264,12 @@ template <int N> __device__ __forceinline__ MlpCtx mlp_ctx(MlpLds<N>& L, int lan
 
 // V and dV/dx of the TL tiles whose state rows are in xs (one environment per lane, identical in both lane
 // halves).  On return every lane holds its environment's V and (if want_grad) gradient.
-template <typename S, int TL, int ACT = HJBX_ACT_RELU>
+// SOFT selects the head: false (PD, controller/vhjb.py) V = |y|^2 + eps_s |e|^2, dV/dy = 2y;  true (soft-PD, `bias` = the LDS copy of
+// MlpBias) every layer adds its bias, layer 3 is activated too and V = h3 . w4 + b4, so backward 3 starts from w4 . act'(a3) and there is
+// no eps_s term.  The chains are the same in both.
+template <typename S, int TL, int ACT = HJBX_ACT_RELU, bool SOFT = false>
 __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtx& c, const float (&xs)[TL][S::N],
-                                               bool want_grad, float (&V)[TL], float (&g)[TL][S::N]) {
+                                               bool want_grad, float (&V)[TL], float (&g)[TL][S::N], const MlpBias* bias = nullptr) {
     constexpr int N = S::N;
     constexpr int NP = MlpLds<N>::NP;
     const int h = c.h;
@@ -253,7 +290,8 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
 
     // ---- layer 1: H1' (128 x 32) = W1' (128 x N) . Z' (N x 32) --------------------------------------
     f32x16 a1[TL][4];
-    zero_acc(a1);
+    if constexpr (SOFT) bias_acc(a1, bias->b1, h);
+    else zero_acc(a1);
     mfma_chain<OffW1F, N / 2, 4, 2, TL>(a1, ring4, c.w1f, [&](int st, int t) { return h ? z[t][2 * st + 1] : z[t][2 * st]; });
 
     // Element-wise work between the products (ReLU, mask, 2y, |y|^2) is done in place on the accumulators in short
@@ -276,7 +314,8 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
                 }
             }
     f32x16 a2[TL][4];
-    zero_acc(a2);
+    if constexpr (SOFT) bias_acc(a2, bias->b2, h);
+    else zero_acc(a2);
     mfma_chain<OffW2F, 64, 4, 2, TL>(a2, ring4, c.w2f, [&](int st, int t) { return a1[t][st >> 4][st & 15]; });
 
     // ---- layer 3: Y' (64 x 32) = W3' . relu(H2') ------------------------------------------------------
@@ -299,10 +338,45 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
                 }
             }
     f32x16 y[TL][2];
-    zero_acc(y);
+    if constexpr (SOFT) bias_acc(y, bias->b3, h);
+    else zero_acc(y);
     mfma_chain<OffW3F, 64, 2, 2, TL>(y, ring2, c.w3f, [&](int st, int t) { return a2[t][st >> 4][st & 15]; });
 
     float vpart[TL];
+    if constexpr (SOFT) {
+        // h3 = act(a3); V = h3 . w4 + b4; the accumulators become dV/da3 = w4 . act'(a3), the start of backward 3
+#pragma unroll
+        for (int t = 0; t < TL; ++t) {
+            f32x2 acc2{0.f, 0.f};
+#pragma unroll
+            for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 w = *reinterpret_cast<const float4*>(bias->w4 + 32 * ob + 8 * q + 4 * h);
+                    const float wv[4] = {w.x, w.y, w.z, w.w};
+                    float hv[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float a = y[t][ob][4 * q + j];
+                        if constexpr (ACT == HJBX_ACT_SIN) {   // act' = cos(a3) cannot be had from sin(a3): both now (see layer 3)
+                            float sn, cs;
+                            sincos1(a, sn, cs);
+                            asm volatile("" : "+v"(sn), "+v"(cs));
+                            hv[j] = sn;
+                            y[t][ob][4 * q + j] = cs * wv[j];
+                            __builtin_amdgcn_sched_barrier(0);
+                        } else {
+                            hv[j] = act1<ACT>(a);
+                            y[t][ob][4 * q + j] = dact1<ACT>(hv[j], wv[j]);
+                        }
+                    }
+                    acc2 = __builtin_elementwise_fma(f32x2{hv[0], hv[1]}, f32x2{wv[0], wv[1]}, acc2);
+                    acc2 = __builtin_elementwise_fma(f32x2{hv[2], hv[3]}, f32x2{wv[2], wv[3]}, acc2);
+                }
+            vpart[t] = acc2[0] + acc2[1];
+            V[t] = vpart[t] + __shfl_xor(vpart[t], 32, 64) + bias->b4;
+        }
+    } else {
 #pragma unroll
     for (int t = 0; t < TL; ++t) {
         f32x2 acc2{0.f, 0.f};  // packed: one v_pk_fma_f32 and one v_pk_add_f32 per two outputs
@@ -318,6 +392,7 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
             }
         vpart[t] = acc2[0] + acc2[1];
         V[t] = vpart[t] + __shfl_xor(vpart[t], 32, 64) + p.eps_s * ee[t];
+    }
     }
     if (!want_grad) return;
 
@@ -342,7 +417,8 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
     // lane dots its 64 resident features with W1' rows (wave-uniform float4 LDS broadcasts) and the two lane
     // halves are added with one cross-half shuffle per row.  [h1 > 0] is re-derived by recomputing layer 1
     // (N/2 x 4 MFMAs, 1 % of the tile): cheaper in issue slots than carrying 128 mask bits per lane.
-    zero_acc(a1);
+    if constexpr (SOFT) bias_acc(a1, bias->b1, h);
+    else zero_acc(a1);
     mfma_chain<OffW1F, N / 2, 4, 2, TL>(a1, ring4, c.w1f, [&](int st, int t) { return h ? z[t][2 * st + 1] : z[t][2 * st]; });
 #pragma unroll
     for (int t = 0; t < TL; ++t) {
@@ -370,7 +446,8 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
         for (int k = 0; k < N; ++k) {
             const float pk = part[k >> 1][k & 1];
             const float v = pk + __shfl_xor(pk, 32, 64);
-            g[t][k] = v * p.istd[k] + 2.f * p.eps_s * e[t][k];
+            if constexpr (SOFT) g[t][k] = v * p.istd[k];
+            else g[t][k] = v * p.istd[k] + 2.f * p.eps_s * e[t][k];
         }
     }
 }

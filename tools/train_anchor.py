@@ -31,6 +31,9 @@ def main():
                     "controller first (BASELINE configs[2]: acrobot energy-shaping warm-start + vhjb)")
     ap.add_argument("--arithmetic", default=None, choices=["f32", "bf16x3", "f16x2"], help="value-network arithmetic of the fused kernels "
                     "(HJBX_OPT_MLP_ARITHMETIC; default: the library's = f32)")
+    ap.add_argument("--structure", default="pd", choices=["pd", "soft_pd"], help="value network: pd = controller/vhjb.py; soft_pd = the "
+                    "notebooks' SoftPDValueApproximator (biases, scalar output, hinge on V(xf))")
+    ap.add_argument("--warmup_epochs", type=int, default=0, help="soft_pd: epochs fitting |V - e'Pe| first (notebooks: 20)")
     args = ap.parse_args()
     if args.arithmetic:
         from q_learning_with_hjb_amd import _abi
@@ -41,8 +44,19 @@ def main():
                     regularization_end_value=0.0)
         if args.env == "quadrotors2DHovering":      # examples/drone_hovering.ipynb cell 4 uses a wider position box than the gin file
             over.update(obs_min=[-3, -3, -1.5, -5, -5, -2], obs_max=[3, 3, 1.5, 5, 5, 2])
-    dyn, pol, mb = load_systems(args.env, epochs=args.epochs, num_of_trajectories_per_epoch=args.trajectories, seed=args.seed,
-                                activation=args.activation, **over)
+    cfg_kw = dict(epochs=args.epochs, num_of_trajectories_per_epoch=args.trajectories, seed=args.seed, **over)
+    dyn, pol, mb = load_systems(args.env, activation=args.activation, **cfg_kw)
+    if args.structure == "soft_pd":
+        # load_systems builds the PD controller; the soft-PD one gets the same dynamics and stock configuration (the constructor re-seeds
+        # from config.seed, so the run is that of a freshly built soft-PD controller).  The soft-PD cell of examples/cartpole_balancing.ipynb
+        # (11) trains on the unnormalised residual |dV/dt + l| ("when using warmup, the unnormalized hjb loss seem work better").
+        from q_learning_with_hjb_amd import _abi as _R
+        from q_learning_with_hjb_amd.controller.vhjb import VHJBController
+        from q_learning_with_hjb_amd.scripts.test_vhjb_policy import _ENVS
+        del pol
+        pol = VHJBController(dyn, _ENVS[args.env][3](**cfg_kw), activation=args.activation, value_structure="soft_pd",
+                             soft_pd_warmup_epochs=args.warmup_epochs,
+                             residual_mode=_R.RESIDUAL_RAW if args.notebook else _R.RESIDUAL_NORMALISED)
     if args.notebook:      # 256 copies of xf, not a box around it
         rb = pol.replay_buffer
         rb.x[:rb.size] = torch.as_tensor(np.asarray(pol.xf, np.float64), dtype=rb.x.dtype, device=rb.x.device)
@@ -57,15 +71,16 @@ def main():
     from q_learning_with_hjb_amd import _abi as _A
     prev = _A.set_option(_A.OPT_MLP_ARITHMETIC, -1)
     cost_by_arithmetic = {}
-    if args.activation == "relu":
+    if args.activation == "relu" and args.structure == "pd":     # (the soft-PD kernels are float32 only)
         for nm, v in (("f32", 0), ("bf16x3", 1), ("f16x2", 2)):
             _A.set_option(_A.OPT_MLP_ARITHMETIC, v)
             np.random.seed(123)
             cost_by_arithmetic[nm] = float(test_policy(pol, dyn, mb, T=args.T, batch=args.starts)["cost_learned"].sum(0).mean())
         _A.set_option(_A.OPT_MLP_ARITHMETIC, prev)
-    print(json.dumps(dict(env=args.env, seed=args.seed, arithmetic=args.arithmetic or "f32", activation=args.activation, fused_param_grad=bool(pol.fused_param_grad), device_driven_fit=bool(pol._fit_graph is not None), notebook=args.notebook, epochs=args.epochs,
+    print(json.dumps(dict(env=args.env, seed=args.seed, arithmetic=args.arithmetic or "f32", activation=args.activation, structure=args.structure, warmup_epochs=args.warmup_epochs, fused_param_grad=bool(pol.fused_param_grad), device_driven_fit=bool(pol._fit_graph is not None), notebook=args.notebook, epochs=args.epochs,
                           warm_start=None if ws is None else dict(records=ws["records"], average_trajectory_cost=round(ws["average_trajectory_cost"], 2)), updates=pol.update_counter, train_seconds=round(train_s, 1),
                           replay_records=len(pol.replay_buffer), avg_traj_len_first=lists[2][0], avg_traj_len_last=lists[2][-1],
+                          total_loss_first=lists[3][0] if lists[3] else None, total_loss_last=lists[3][-1] if lists[3] else None,
                           hjb_loss_first=lists[4][0] if lists[4] else None, hjb_loss_last=lists[4][-1] if lists[4] else None,
                           mean_cost_learned=float(cl.mean()), mean_cost_model_based=float(cm.mean()), mean_cost_learned_by_eval_arithmetic=cost_by_arithmetic,
                           per_start_learned=[round(float(v), 3) for v in cl], per_start_model_based=[round(float(v), 3) for v in cm])))
