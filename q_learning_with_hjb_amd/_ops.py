@@ -6,7 +6,9 @@ public `Dynamics` / `Controller` classes do the numpy <-> device marshalling aro
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import threading
 
 import torch
 
@@ -48,30 +50,73 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-_ws = {}
+class Workspaces:
+    """The library's device scratch for one device, each buffer allocated on first use: the arrival tickets of the reducing entry points
+    (`reduce`), the work-distribution words of the persistent rollout kernel (`rollout`) and the parameter-gradient scratch (`grad`).
+    Tickets and words are zero-filled ONCE; every launch that runs to completion leaves them at zero (include/hjbx.h).
+
+    `owned=True` is the set of a captured graph, which replays into the raw pointers of whatever the capture was handed: it never frees
+    or replaces a buffer it has handed out.  The eager sets of `_workspaces` (`owned=False`) give a much larger gradient scratch back."""
+
+    def __init__(self, device, owned=True):
+        self.device, self.owned = torch.device(device), owned
+        self._reduce = self._rollout = self._grad = None
+        self._retired = []
+
+    def reduce(self) -> torch.Tensor:
+        if self._reduce is None:
+            self._reduce = torch.zeros((lib().hjbx_reduce_workspace_bytes() + 15) // 16 * 2, dtype=torch.float64, device=self.device)
+        return self._reduce
+
+    def rollout(self) -> torch.Tensor:
+        if self._rollout is None:
+            self._rollout = torch.zeros((lib().hjbx_rollout_workspace_bytes() + 15) // 16 * 4, dtype=torch.int32, device=self.device)
+        return self._rollout
+
+    def grad(self, need: int) -> torch.Tensor:
+        """At least `need` bytes of uninitialised scratch: grown on demand; an eager set also gives a much larger one back."""
+        ws = self._grad
+        if ws is None or ws.numel() < need or (not self.owned and ws.numel() > 4 * need + (64 << 20)):
+            if self.owned and ws is not None:
+                self._retired.append(ws)          # a graph captured with it may still replay into it
+            ws = self._grad = None                # (an eager set hands the old buffer back to the allocator before taking the new one)
+            ws = self._grad = torch.empty((need + 255) // 256 * 256, dtype=torch.uint8, device=self.device)
+        return ws
 
 
-def _workspace(device) -> torch.Tensor:
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    w = _ws.get(key)
-    if w is None:
-        # zero-filled ONCE: the reducing kernels keep their arrival counters in it and leave them at zero (include/hjbx.h)
-        w = torch.zeros((lib().hjbx_reduce_workspace_bytes() + 15) // 16 * 2, dtype=torch.float64, device=device)
-        _ws[key] = w
-    return w
+_eager = {}                  # (device index, stream handle) -> the Workspaces of eager launches on that stream
+_active = threading.local()
 
 
-_rws = {}
+@contextlib.contextmanager
+def using_workspaces(ws: Workspaces):
+    """Inside the block, every call on this thread takes its workspaces from `ws` (a capture owner's set) instead of the eager set of its
+    stream.  Thread-local is enough: the workspaces are only requested by forward code on the calling thread -- the backward passes of
+    _HJBResidualSum and _TerminationResidualSum, which autograd may run on another thread, only multiply saved tensors."""
+    prev = getattr(_active, "ws", None)
+    _active.ws = ws
+    try:
+        yield ws
+    finally:
+        _active.ws = prev
+
+
+def _workspaces(device) -> Workspaces:
+    """The set an `_ops` call on `device` passes to its kernel: the one `using_workspaces` activated, else the eager set of the stream
+    the call launches on."""
+    ws = getattr(_active, "ws", None)
+    if ws is not None:
+        return ws
+    key = (device.index, _stream())
+    ws = _eager.get(key)
+    if ws is None:
+        ws = _eager[key] = Workspaces(device, owned=False)
+    return ws
 
 
 def _rollout_workspace(device) -> torch.Tensor:
-    """Work-distribution words of the persistent rollout kernel: zero-filled once, left zeroed by every launch; one per stream."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    w = _rws.get(key)
-    if w is None:
-        w = torch.zeros((lib().hjbx_rollout_workspace_bytes() + 15) // 16 * 4, dtype=torch.int32, device=device)
-        _rws[key] = w
-    return w
+    """The work-distribution words the persistent rollout kernel launched now on `device` gets (tests read them to check they are left zeroed)."""
+    return _workspaces(device).rollout()
 
 
 def _fn(name, t):
@@ -161,7 +206,7 @@ def hjb_residual(sys, task, x, grad_v, done, mode=_abi.RESIDUAL_NORMALISED, want
     li = torch.empty((B,), dtype=x.dtype, device=x.device) if want_loss else None
     dg = torch.empty_like(x) if want_grad else None
     sums = torch.empty((3,), dtype=x.dtype, device=x.device) if want_sums else None
-    ws = _workspace(x.device) if want_sums else None
+    ws = _workspaces(x.device).reduce() if want_sums else None
     check(_fn("hjb_residual", x)(sys.ptr, ref(task), int(mode), _p(x), _p(grad_v), _p(done), _p(li), _p(dg), _p(sums),
                                  _p(ws), B, _stream()))
     return li, dg, sums
@@ -175,7 +220,7 @@ def termination_residual(eps, V, cost, done, want_loss=True, want_grad=True, wan
     li = torch.empty_like(V) if want_loss else None
     dv = torch.empty_like(V) if want_grad else None
     sums = torch.empty((3,), dtype=V.dtype, device=V.device) if want_sums else None
-    ws = _workspace(V.device) if want_sums else None
+    ws = _workspaces(V.device).reduce() if want_sums else None
     check(_fn("termination_residual", V)(float(eps), _p(V), _p(cost), _p(done), _p(li), _p(dv), _p(sums), _p(ws), B, _stream()))
     return li, dv, sums
 
@@ -289,9 +334,6 @@ def _mfma_rollout(entry, sys, task, mlp_desc, x, n_steps, T_max, done_step, t_fi
     return dict(traj=traj, u=ulog, cost=cost, done=done, residual=resid, x_out=x_out)
 
 
-_tws = {}
-
-
 def value_loss_grad(sys, task, mlp_desc, x, cost, done, mode=_abi.RESIDUAL_NORMALISED, out=None):
     """Fused parameter gradient of the value-learning step (f32, relu): -> flat (2P + 4,) =
     [d sum(hjb)/dW1 | dW2 | dW3 | d sum(termination)/dW1 | dW2 | dW3 | sum hjb, sum termination, #interior, #done]."""
@@ -302,21 +344,9 @@ def value_loss_grad(sys, task, mlp_desc, x, cost, done, mode=_abi.RESIDUAL_NORMA
     P = sys.n * mlp_desc.h1 + mlp_desc.h1 * mlp_desc.h2 + mlp_desc.h2 * mlp_desc.h3
     flat = torch.empty((2 * P + 4,), dtype=torch.float32, device=x.device) if out is None else out
     _chk(flat, "out", (2 * P + 4,), torch.float32)
-    ws = _train_workspace(x.device, lib().hjbx_value_loss_grad_workspace_bytes(B))
+    ws = _workspaces(x.device).grad(lib().hjbx_value_loss_grad_workspace_bytes(B))
     check(lib().hjbx_value_loss_grad_f32(sys.ptr, ref(task), ref(mlp_desc), int(mode), _p(x), _p(cost), _p(done), _p(flat), _p(ws), B, _stream()))
     return flat
-
-
-def _train_workspace(device, need):
-    """The per-(device, stream) scratch of the parameter-gradient entry points: grown on demand, a much larger one given back."""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _tws.get(key)
-    if ws is None or ws.numel() < need or ws.numel() > 4 * need + (64 << 20):
-        ws = None
-        _tws.pop(key, None)
-        ws = torch.empty((need + 255) // 256 * 256, dtype=torch.uint8, device=device)
-        _tws[key] = ws
-    return ws
 
 
 def _adam_struct(params, exp_avgs, exp_avg_sqs, steps, ticket, lr, beta1, beta2, adam_eps):
@@ -374,20 +404,19 @@ def value_loss_adam(sys, task, mlp_desc, x, cost, done, mode, regularization, ep
         _chk(loss_accum, "loss_accum", (3,), torch.float32)
     if step_counter is not None:
         _chk(step_counter, "step_counter", (1,), torch.int32)
-    ws = _train_workspace(x.device, lib().hjbx_value_loss_adam_workspace_bytes(B))
+    ws = _workspaces(x.device).grad(lib().hjbx_value_loss_adam_workspace_bytes(B))
     check(lib().hjbx_value_loss_adam_f32(sys.ptr, ref(task), ref(mlp_desc), int(mode), _p(x), _p(cost), _p(done), reg_dev, reg, float(eps), C.byref(st), _p(losses),
                                          _p(loss_accum), _p(step_counter), None if next_mb is None else C.byref(next_mb), _p(ws), B, _stream()))
     return losses
 
 
 def release_workspaces(stream=None):
-    """Drop the cached workspaces (reduce tickets, rollout flags, parameter-gradient scratch) of one stream handle, or of every stream
-    (`stream=None`).  They are re-created -- zero-filled where the kernels need that -- on next use.  Call it when a stream goes away, or
-    after a launch was aborted (a device fault, a killed kernel): the ticket / flag words are only guaranteed to be zero after launches
-    that ran to completion."""
-    for cache in (_ws, _rws, _tws):
-        for key in [k for k in cache if stream is None or k[1] == stream]:
-            del cache[key]
+    """Drop the eager workspace sets (reduce tickets, rollout flags, parameter-gradient scratch) of one stream handle, or of every stream
+    (`stream=None`).  They are re-created -- zero-filled where the kernels need that -- on next use.  The sets owned by captured graphs
+    are not touched: they live exactly as long as their owner.  Call it when a stream goes away, or after an eager launch was aborted (a
+    device fault, a killed kernel): the ticket / flag words are only guaranteed to be zero after launches that ran to completion."""
+    for key in [k for k in _eager if stream is None or k[1] == stream]:
+        del _eager[key]
 
 
 def mix_gradients(flat, n_params, regularization, eps, loss_accum=None, step_counter=None):

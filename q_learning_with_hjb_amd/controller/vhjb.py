@@ -903,16 +903,8 @@ class GraphedStep:
     def __init__(self, optimizer, params, core, example_inputs):
         self.inputs = [t.detach().clone() for t in example_inputs]
         self.shapes = [tuple(t.shape) for t in self.inputs]
-        self._stream, self.graph, self.out = capture_step(optimizer, params, lambda: core(*self.inputs), self.inputs[0].device)
-
-    def __del__(self):
-        # the workspaces cached for this step's private stream die with it (5 KB of scratch per sample for the parameter gradient)
-        st = getattr(self, "_stream", None)
-        if st is not None:
-            try:
-                _ops.release_workspaces(st.cuda_stream)
-            except Exception:
-                pass
+        self.workspaces = _ops.Workspaces(self.inputs[0].device)
+        self.graph, self.out = capture_step(optimizer, params, lambda: core(*self.inputs), self.inputs[0].device, self.workspaces)
 
     def matches(self, *inputs) -> bool:
         return [tuple(t.shape) for t in inputs] == self.shapes
@@ -937,18 +929,15 @@ def adam_state(optimizer, params):
     return [st[p]["exp_avg"] for p in params], [st[p]["exp_avg_sq"] for p in params], [st[p]["step"] for p in params]
 
 
-def capture_step(optimizer, params, step_fn, dev, before_each=None):
+def capture_step(optimizer, params, step_fn, dev, workspaces, before_each=None):
     """Warm `step_fn` up three times and capture it into a hipGraph, leaving parameters and optimiser state as they were.
-    -> (the private stream the graph was captured on, the graph, step_fn's captured outputs)"""
+    -> (the graph, step_fn's captured outputs)"""
     saved_p = [p.detach().clone() for p in params]
     saved_s = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in optimizer.state[p].items()} for p in params if p in optimizer.state}
-    # warm-up AND capture run on this one side stream: the library's workspaces (_ops: reduce tickets, rollout flags, the parameter-
-    # gradient scratch) are cached per (device, stream), so the buffers the warm-up allocated -- and zero-filled, outside any capture --
-    # are exactly the ones the captured launches use (capturing on torch's default capture stream allocated every workspace a second
-    # time, in the graph's pool, and recorded their zero-fill as memset nodes)
+    # warm-up and capture take the library's workspaces (_ops.Workspaces) from `workspaces`, which the caller keeps alive as long as the graph
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
+    with torch.cuda.stream(side), _ops.using_workspaces(workspaces):
         for _ in range(3):                      # allocates Adam's state, rocBLAS workspaces and this library's workspaces
             if before_each is not None:
                 before_each()
@@ -972,12 +961,12 @@ def capture_step(optimizer, params, step_fn, dev, before_each=None):
     gc.collect()
     gc.disable()
     try:
-        with torch.cuda.graph(graph, stream=side):
+        with torch.cuda.graph(graph, stream=side), _ops.using_workspaces(workspaces):
             out = step_fn()
     finally:
         if was_enabled:
             gc.enable()
-    return side, graph, out
+    return graph, out
 
 
 class FitGraph:
@@ -1005,7 +994,10 @@ class FitGraph:
         self.dones = torch.empty((batch,), dtype=torch.float32, device=dev)
         self.reg = torch.zeros((), dtype=torch.float32, device=dev)
         self._ctl_ref = weakref.ref(ctl)      # (no reference cycle: the graphs die with the controller, not at some later garbage collection)
-        self._streams, self._graphs = [], {}
+        self._graphs = {}
+        # one set for the 1-step and the UNROLL graph: both replay in order on the current stream, and capture_step's side stream waits
+        # for the current stream before the second warm-up
+        self.workspaces = _ops.Workspaces(dev)
         # two kernels per update when the one-call update is in use: its epilogue gathers the next minibatch
         self.fused_next = ctl._one_call_update()
         self._next_mb = _ops.next_minibatch(rb.x, rb.cost, rb.done, self.perm, self.reg_table, self.xs, self.costs, self.dones, self.reg) if self.fused_next else None
@@ -1041,11 +1033,11 @@ class FitGraph:
             self.step.zero_()
             self.begin_epoch()
 
-        stream, graph, out = capture_step(ctl.optimizer, list(ctl.value_function_approximator.parameters()), step_fn, ctl.device, before_each=before_each)
+        graph, out = capture_step(ctl.optimizer, list(ctl.value_function_approximator.parameters()), step_fn, ctl.device, self.workspaces,
+                                  before_each=before_each)
         self.step.copy_(saved[0])
         self.loss_accum.copy_(saved[1])
         self.begin_epoch()                     # (the warm-up runs left another minibatch in the input buffers: gather the current one again)
-        self._streams.append(stream)
         self._graphs[count] = (graph, out)
 
     def replay(self, count: int):
@@ -1057,14 +1049,6 @@ class FitGraph:
             count -= self.UNROLL
         for _ in range(count):
             self._graphs[1][0].replay()
-
-    def __del__(self):
-        for st in getattr(self, "_streams", ()):
-            try:
-                _ops.release_workspaces(st.cuda_stream)
-            except Exception:
-                pass
-
 
 
 # ------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ xs, dones, costs = _batch(d, ctl, 256, 3)
 for _ in range(5):
     flat = _ops.value_loss_grad(d.system, ctl._task, vf.descriptor(), xs, costs, dones)
 torch.cuda.synchronize()
-ws = list(_ops._tws.values())[0]
+ws = _ops._workspaces(xs.device).grad(_abi.lib().hjbx_value_loss_grad_workspace_bytes(xs.shape[0]))
 grid, n = 32, 4
 partial = (grid * 48 * 1024 * 4 + 255) // 256 * 256
 rec = ws[partial + 1 * 2 * (2 * n * 128) * 4:][:64 * 8].cpu().numpy().view(np.uint64)
