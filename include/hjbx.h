@@ -33,6 +33,7 @@ extern "C" {
 #endif
 
 #define HJBX_VERSION 112 /* major*100 + minor */
+#define HJBX_HAS_REPLAY_APPEND 1 /* hjbx_replay_append_f32 / _f64 exist (added without a version step: an addition, nothing else changed) */
 #define HJBX_MAX_N 10    /* largest state dimension (NearHoverQuadcopter) */
 #define HJBX_MAX_M 3     /* largest control dimension */
 
@@ -429,6 +430,29 @@ int hjbx_value_loss_adam_f32(const hjbx_system* sys, const hjbx_task* task, cons
 int hjbx_replay_gather_f32(const float* buf_x, const float* buf_cost, const float* buf_done, int64_t capacity, int n, const int32_t* perm,
                            int64_t perm_len, const int32_t* step_dev, const float* reg_table, int64_t table_len, int64_t batch, float* xs,
                            float* costs, float* dones, float* reg_out, void* stream);
+
+/* A rollout log appended to the device-resident replay ring, trajectory by trajectory: `trajectory = rollout_trajectory();
+ * replay_buffer.xs.extend(trajectory)` of the reference (vhjb.py:304-308) on its deque(maxlen) (vhjb.py:62-73), for B closed loops at once and
+ * without leaving the log's time-major layout.
+ *   traj (T+1, B, n), cost (T+1, B): the log; done_step (B,) int32: index of each environment's terminal tuple;
+ *   buf_x (capacity, n), buf_cost, buf_done (capacity,): the ring; head: its next write slot, in [0, capacity).
+ * Environment b emits L_b = done_step[b] + 1 records (t = 0 .. done_step[b], in time order), environments in order of b.  With off_b the
+ * exclusive prefix sum of L, K = sum L_b and drop = max(0, K - capacity), record (b, t) has the running index j = off_b + t; it is written
+ * iff j >= drop, to slot (head + j - drop) mod capacity: x and cost copied bit for bit, done = 1 for t == done_step[b], else 0.  Nothing
+ * beyond done_step[b] is read, no other slot is written, and the work is proportional to the min(K, capacity) records that land, not to
+ * B (T+1).  The caller advances head by min(K, capacity) mod capacity.
+ * A done_step entry outside [0, T] makes the call append NOTHING (no out-of-bounds access for any content of done_step).
+ *   header: int64[4] in device memory = { K (over the valid entries), drop, number of out-of-range done_step entries, 0 }.
+ *   workspace: hjbx_replay_append_workspace_bytes(B) bytes, 8-byte aligned, need not be initialised (slice sums and offsets of this call).
+ * HJBX_EINVAL before any launch: a NULL or misaligned buffer, n outside [1, HJBX_MAX_N], B < 0, T < 0, capacity < 1, head outside
+ * [0, capacity).  B == 0: HJBX_OK, nothing launched, the header zeroed. */
+size_t hjbx_replay_append_workspace_bytes(int64_t B);
+/* (vhjb.py:304-308 for float32 logs) */
+int hjbx_replay_append_f32(const float* traj, const float* cost, const int32_t* done_step, int64_t T, int64_t B, int n, float* buf_x,
+                           float* buf_cost, float* buf_done, int64_t capacity, int64_t head, int64_t* header, void* workspace, void* stream);
+/* (vhjb.py:304-308 for float64 logs) */
+int hjbx_replay_append_f64(const double* traj, const double* cost, const int32_t* done_step, int64_t T, int64_t B, int n, double* buf_x,
+                           double* buf_cost, double* buf_done, int64_t capacity, int64_t head, int64_t* header, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

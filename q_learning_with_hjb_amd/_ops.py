@@ -52,7 +52,8 @@ def _p(t):
 
 class Workspaces:
     """The library's device scratch for one device, each buffer allocated on first use: the arrival tickets of the reducing entry points
-    (`reduce`), the work-distribution words of the persistent rollout kernel (`rollout`) and the parameter-gradient scratch (`grad`).
+    (`reduce`), the work-distribution words of the persistent rollout kernel (`rollout`), the parameter-gradient scratch (`grad`) and the
+    slice offsets of the replay append (`append`).
     Tickets and words are zero-filled ONCE; every launch that runs to completion leaves them at zero (include/hjbx.h).
 
     `owned=True` is the set of a captured graph, which replays into the raw pointers of whatever the capture was handed: it never frees
@@ -60,7 +61,7 @@ class Workspaces:
 
     def __init__(self, device, owned=True):
         self.device, self.owned = torch.device(device), owned
-        self._reduce = self._rollout = self._grad = None
+        self._reduce = self._rollout = self._grad = self._append = None
         self._retired = []
 
     def reduce(self) -> torch.Tensor:
@@ -81,6 +82,16 @@ class Workspaces:
                 self._retired.append(ws)          # a graph captured with it may still replay into it
             ws = self._grad = None                # (an eager set hands the old buffer back to the allocator before taking the new one)
             ws = self._grad = torch.empty((need + 255) // 256 * 256, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def append(self, need: int) -> torch.Tensor:
+        """At least `need` bytes of uninitialised scratch for hjbx_replay_append_*: grown on demand (4 bytes per 21 environments: never worth
+        giving back)."""
+        ws = self._append
+        if ws is None or ws.numel() < need:
+            if self.owned and ws is not None:
+                self._retired.append(ws)
+            ws = self._append = torch.empty((need + 255) // 256 * 256, dtype=torch.uint8, device=self.device)
         return ws
 
 
@@ -466,3 +477,31 @@ def replay_gather(buf_x, buf_cost, buf_done, perm, step_counter, reg_table, xs, 
     _chk(reg_table, "reg_table", (reg_table.shape[0],), torch.float32)
     check(lib().hjbx_replay_gather_f32(_p(buf_x), _p(buf_cost), _p(buf_done), int(buf_x.shape[0]), int(n), _p(perm), int(perm.shape[0]), _p(step_counter),
                                        _p(reg_table), int(reg_table.shape[0]), int(batch), _p(xs), _p(costs), _p(dones), _p(reg_out), _stream()))
+
+
+def replay_append(traj, cost, done_step, buf_x, buf_cost, buf_done, head):
+    """hjbx_replay_append_f32 / _f64: the tuples t <= done_step[b] of a time-major rollout log (traj (T+1, B, n), cost (T+1, B)) appended to the
+    replay ring (buf_x (capacity, n), buf_cost, buf_done (capacity,)) whose next write slot is `head`, trajectory by trajectory, keeping the
+    last `capacity` of them.  -> header, a (4,) int64 DEVICE tensor [records emitted K, records dropped, out-of-range done_step entries, 0];
+    with a nonzero third entry nothing was appended.  Nothing here synchronises: the caller reads the header when it needs the counts."""
+    T1, B, n = traj.shape
+    capacity = buf_x.shape[0]
+    _sfx(traj)
+    _chk(traj, "traj", (T1, B, n))
+    _chk(cost, "cost", (T1, B), traj.dtype)
+    _chk(done_step, "done_step", (B,), torch.int32)
+    _chk(buf_x, "buf_x", (capacity, n), traj.dtype)
+    _chk(buf_cost, "buf_cost", (capacity,), traj.dtype)
+    _chk(buf_done, "buf_done", (capacity,), traj.dtype)
+    for t, nm in ((cost, "cost"), (done_step, "done_step"), (buf_x, "buf_x"), (buf_cost, "buf_cost"), (buf_done, "buf_done")):
+        if t.device != traj.device:
+            raise ValueError(f"{nm} is on {t.device}, traj on {traj.device}")
+    if T1 < 1:
+        raise ValueError("traj needs at least one time step")
+    if B == 0:                        # (empty tensors have no address to hand over)
+        return torch.zeros((4,), dtype=torch.int64, device=traj.device)
+    header = torch.empty((4,), dtype=torch.int64, device=traj.device)
+    ws =_workspaces(traj.device).append(lib().hjbx_replay_append_workspace_bytes(B))
+    check(_fn("replay_append", traj)(_p(traj), _p(cost), _p(done_step), T1 - 1, B, n, _p(buf_x), _p(buf_cost), _p(buf_done), capacity, int(head),
+                                     _p(header), _p(ws), _stream()))
+    return header

@@ -321,6 +321,38 @@ class ReplayBuffer:
         self.head = (self.head + k) % self.capacity
         self.size = min(self.capacity, self.size + k)
 
+    def extend_rollout(self, traj: torch.Tensor, cost: torch.Tensor, done_step: torch.Tensor) -> int:
+        """Append the tuples t <= done_step[b] of a time-major rollout log (traj (T+1, B, n), cost (T+1, B), done_step (B,) int32), trajectory
+        by trajectory (vhjb.py:304-308), with done = 1 on each trajectory's last tuple.  Returns the number of records emitted, K; the ring
+        keeps the last `capacity` of them.  Device logs go through hjbx_replay_append_* (no transposed copy of the log, work proportional to
+        what lands, one read-back of four integers); a done_step entry outside [0, T] raises ValueError and leaves the ring as it was."""
+        T = traj.shape[0] - 1
+        message = "extend_rollout: {} done_step entries outside [0, {}]; nothing was appended"
+        if not (traj.is_cuda and traj.dtype in (torch.float32, torch.float64)):
+            bad = int(((done_step < 0) | (done_step > T)).sum().item())
+            if bad:
+                raise ValueError(message.format(bad, T))
+            return self._extend_rollout_torch(traj, cost, done_step)
+        K, _drop, bad = _ops.replay_append(traj, cost, done_step, self.x, self.cost, self.done, self.head).tolist()[:3]
+        if bad:
+            raise ValueError(message.format(bad, T))
+        k = min(K, self.capacity)
+        self.head = (self.head + k) % self.capacity
+        self.size = min(self.capacity, self.size + k)
+        return K
+
+    def _extend_rollout_torch(self, traj: torch.Tensor, cost: torch.Tensor, done_step: torch.Tensor) -> int:
+        """extend_rollout through torch: a transposed copy of the log, a boolean-mask compaction, then `extend`.  The path of CPU tensors, and
+        what the device path is compared against.  (Its cost grows with B (T+1), not with what lands; and on the MI355X its masked transposed
+        copy of a 3.4 GB log -- cartpole, B = 2^20, T = 200 -- was observed to deliver all-zero states, see tests/test_gpu_replay_append.py.)"""
+        ds = done_step.long()
+        steps = torch.arange(traj.shape[0], device=traj.device)[:, None]
+        valid = steps <= ds[None, :]                                  # (T+1, B): tuples up to and including the terminal one
+        done = (steps == ds[None, :]).to(traj.dtype)
+        vm = valid.t().reshape(-1)  # trajectory-major, like extending the deque trajectory by trajectory
+        self.extend(traj.transpose(0, 1).reshape(-1, traj.shape[2])[vm], cost.t().reshape(-1)[vm], done.t().reshape(-1)[vm])
+        return int(vm.sum().item())
+
     def num_batches(self, batch_size: int) -> int:
         return self.size // batch_size
 
@@ -349,7 +381,8 @@ class VHJBController(Controller):
     def __init__(self, dynamics: Dynamics, config, device=None, dtype=torch.float32, process_group=None,
                  residual_mode=_abi.RESIDUAL_NORMALISED, fused_value_grad: Optional[bool] = None,
                  graph_updates: Optional[bool] = None, activation: str = "relu", fused_param_grad: Optional[bool] = None,
-                 value_structure: str = "pd", soft_pd_regularization: float = 1.0, soft_pd_warmup_epochs: int = 0) -> None:
+                 value_structure: str = "pd", soft_pd_regularization: float = 1.0, soft_pd_warmup_epochs: int = 0,
+                 device_replay_append: bool = True) -> None:
         super().__init__()
         # value_structure: "pd" = ValueFunctionApproximator (controller/vhjb.py); "soft_pd" = SoftPDValueFunctionApproximator, trained with
         # the hinge soft_pd_regularization * mean(relu(V(xf) - V(x))) on top of the HJB loss, after soft_pd_warmup_epochs epochs of fitting
@@ -471,6 +504,8 @@ class VHJBController(Controller):
         interior = draw(config.num_of_interior_data, config.interior_states_mean, config.interior_states_std)
         boundary = draw(config.num_of_boundary_data, config.boundary_states_mean, config.boundary_states_std)
         self.replay_buffer = ReplayBuffer(n, config.maximum_buffer_size, dtype, self.device)
+        # rollout logs reach the ring through hjbx_replay_append_*; device_replay_append=False or HJBX_DEVICE_APPEND=0 keeps the torch expression
+        self.device_replay_append = bool(device_replay_append) and self.device.type == "cuda" and os.environ.get("HJBX_DEVICE_APPEND", "1") != "0"
         if interior.shape[0]:
             interior = _ops.wrap(dynamics.system, interior)
             z = torch.zeros(interior.shape[0], dtype=dtype, device=self.device)
@@ -612,13 +647,16 @@ class VHJBController(Controller):
         ds = out["done_step"].long()
         steps = torch.arange(T + 1, device=self.device)[:, None]
         valid = steps <= ds[None, :]                                  # (T+1, B): tuples up to and including the terminal one
-        done = (steps == ds[None, :]).to(self.dtype)
-        vm = valid.t().reshape(-1)
-        self.replay_buffer.extend(out["traj"].transpose(0, 1).reshape(-1, self.state_dim)[vm], out["cost"].t().reshape(-1)[vm],
-                                  done.t().reshape(-1)[vm])
+        records = self._append_rollout(out)
         costs = (out["cost"] * valid).sum(0)
-        return dict(records=int(vm.sum().item()), average_trajectory_cost=float(costs.mean().item()),
+        return dict(records=records, average_trajectory_cost=float(costs.mean().item()),
                     average_trajectory_length=float((ds + 1).double().mean().item()), done_step=out["done_step"])
+
+    def _append_rollout(self, out) -> int:
+        """`replay_buffer.xs.extend(trajectory)` for every trajectory of a rollout log (vhjb.py:304-308) -> the number of tuples it holds."""
+        rb = self.replay_buffer
+        append = rb.extend_rollout if self.device_replay_append else rb._extend_rollout_torch
+        return append(out["traj"], out["cost"], out["done_step"])
 
     def rollout_trajectory(self) -> List[Tuple[np.ndarray, float, float]]:
         """One trajectory as the reference returns it: a list of (x, cost, done) tuples."""
@@ -842,10 +880,7 @@ class VHJBController(Controller):
                 ds = out["done_step"].long()
                 valid = (torch.arange(self.maximum_timestep + 1, device=self.device)[:, None] <= ds[None, :])  # (T+1, B)
                 traj_costs = (out["cost"] * valid).sum(0).double().cpu().numpy()
-                trajectory_lengths = int((ds + 1).sum().item())
-                vm = valid.t().reshape(-1)  # trajectory-major, like extending the deque trajectory by trajectory
-                self.replay_buffer.extend(out["traj"].transpose(0, 1).reshape(-1, self.state_dim)[vm],
-                                          out["cost"].t().reshape(-1)[vm], out["done"].t().reshape(-1)[vm])
+                trajectory_lengths = self._append_rollout(out)        # the number of tuples = the sum of the trajectory lengths
             # fit the value function
             total_losses = hjb_losses = termination_losses = 0.0
             self.train_mode = True
