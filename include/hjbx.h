@@ -34,6 +34,7 @@ extern "C" {
 
 #define HJBX_VERSION 112 /* major*100 + minor */
 #define HJBX_HAS_REPLAY_APPEND 1 /* hjbx_replay_append_f32 / _f64 exist (added without a version step: an addition, nothing else changed) */
+#define HJBX_HAS_USER_MATRIX_CORES 1 /* hjbx_system_enable_matrix_cores / hjbx_system_matrix_cores / hjbx_system_code_object exist (an addition) */
 #define HJBX_MAX_N 10    /* largest state dimension (NearHoverQuadcopter) */
 #define HJBX_MAX_M 3     /* largest control dimension */
 
@@ -230,13 +231,35 @@ void hjbx_system_destroy(hjbx_system* sys);
  * library's own build flags) INTO THE LIBRARY'S OWN STREAMING KERNELS, float32 and float64: the returned handle works with every
  * hjbx_*_f32 / _f64 entry point of the HJBX_DECLARE block below (wrap, affine, dynamics_step, simulate with HJBX_EULER / HJBX_RK4,
  * initial_state, costs, control_from_grad, hjb_residual, vhjb_step, controller and rollout_feedback with HJBX_CTRL_LINEAR_FEEDBACK).
- * The matrix-core entry points (hjbx_value_grad_f32, hjbx_vhjb_rollout_f32, hjbx_value_loss_grad_f32) exist for the built-in systems
- * only and return HJBX_EUNSUPPORTED for such a handle.  Compilation needs no GPU.  HJBX_EINVAL when the source does not compile
+ * The matrix-core entry points (hjbx_value_grad_f32, hjbx_vhjb_rollout_f32, the two hjbx_softpd_* ones, hjbx_value_loss_grad_f32) return
+ * HJBX_EUNSUPPORTED for such a handle unless it asked for them (hjbx_system_enable_matrix_cores below; the parameter gradient stays with
+ * the built-in systems).  Compilation needs no GPU.  HJBX_EINVAL when the source does not compile
  * (hjbx_last_compile_log returns the compiler's messages for the calling thread's last call), HJBX_EUNSUPPORTED when libhiprtc.so
  * is not available. */
 int hjbx_system_create_from_source(int user_kind, const char* device_source, int n, int m, double dt, const double* umin,
                                    const double* umax, const double* params, int n_params, hjbx_system** out);
 size_t hjbx_last_compile_log(char* buf, size_t buflen);
+/* The value network on the matrix cores for a user-defined system: the subclass of Dynamics (dynamics_basic.py:64-94) under the reference's
+ * VHJBController (controller/vhjb.py:17-60 the network, :201-202 its input gradient, :162-193 the closed loop).  Marks a HJBX_SYS_USER
+ * handle as wanting the two persistent matrix-core kernels: from then on hjbx_value_grad_f32, hjbx_vhjb_rollout_f32,
+ * hjbx_softpd_value_grad_f32 and hjbx_softpd_rollout_f32 accept it, with the arguments, workspace, chunking and env_order contract they
+ * have for the built-in systems (HJBX_EULER / HJBX_RK4; the fused rollout is bit-identical to value_grad + hjbx_vhjb_step_f32 per step).
+ * Nothing is compiled here: the first of those calls for a (head, activation) compiles the user's source into the kernels of
+ * csrc/hjbx_user_mlp_kernels.hpp (hiprtc, seconds, once per handle; a source that does not compile there: HJBX_EINVAL +
+ * hjbx_last_compile_log; kernels that would spill registers to scratch: HJBX_EUNSUPPORTED; either way the handle keeps working with the
+ * streaming entry points and the refusal is remembered).  float32 MFMA arithmetic only: with HJBX_OPT_MLP_ARITHMETIC != 0 the PD entry
+ * points return HJBX_EUNSUPPORTED for such a handle.  Call it before the handle is shared between threads.
+ * HJBX_EUNSUPPORTED when n is odd (the kernels walk the state in k-steps of 2); HJBX_EINVAL for a built-in handle. */
+int hjbx_system_enable_matrix_cores(hjbx_system* sys);
+/* 1 when the handle is a user-defined system with the matrix-core kernels enabled, 0 otherwise (built-in systems included). */
+int hjbx_system_matrix_cores(const hjbx_system* sys);
+/* The gfx950 code objects (ELF) a user-defined system runs (dynamics_basic.py:64-94 compiled; vhjb.py:17-60, 162-193, 201-202 for the
+ * matrix-core units), for inspection: copies up to `len` bytes into buf (may be NULL) and returns the object's size.  `which` =
+ * HJBX_CODE_STREAMING, or HJBX_CODE_MATRIX_CORES(head, activation) with head 0 = hjbx_mlp, 1 = hjbx_softpd_mlp -- compiled now if it has not
+ * been yet.  Returns 0 on failure (hjbx_last_error; hjbx_last_compile_log when the compiler refused the source). */
+#define HJBX_CODE_STREAMING 0
+#define HJBX_CODE_MATRIX_CORES(head, activation) (1 + 3 * (head) + (activation))
+size_t hjbx_system_code_object(const hjbx_system* sys, int which, void* buf, size_t len);
 /* Dynamics.get_dimension, dynamics_basic.py:31-36 */
 int hjbx_dims(const hjbx_system* sys, int* n, int* m);
 /* Bytes of device scratch the reducing entry points need (hjb_residual, termination_residual).  The workspace holds the
@@ -350,8 +373,8 @@ int hjbx_vhjb_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const h
 /* The soft-PD network (hjbx_softpd_mlp) in the two fused kernels above: V (B,) and gradV (B,n) as hjbx_value_grad_f32 (V or gradV may be NULL),
  * and the closed loop with exactly the arguments, chunking (t_first, n_steps), in-place done_step, logs, x_out, env_order and rollout
  * workspace of hjbx_vhjb_rollout_f32 (bit-identical to hjbx_softpd_value_grad_f32 + hjbx_vhjb_step_f32 per step).  Always the float32 MFMA
- * arithmetic: HJBX_OPT_MLP_ARITHMETIC does not apply.  Features [128,128,64] and the built-in systems only (HJBX_EUNSUPPORTED otherwise,
- * user-defined systems included).  There is no fused parameter gradient for this network: it is trained through autograd. */
+ * arithmetic: HJBX_OPT_MLP_ARITHMETIC does not apply.  Features [128,128,64]; built-in systems, and user-defined ones after
+ * hjbx_system_enable_matrix_cores (HJBX_EUNSUPPORTED otherwise).  There is no fused parameter gradient for this network: it is trained through autograd. */
 int hjbx_softpd_value_grad_f32(const hjbx_system* sys, const hjbx_softpd_mlp* mlp, const float* x, float* V, float* gradV, int64_t B,
                                void* stream);
 int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const hjbx_softpd_mlp* mlp, int integrator, int t_first,

@@ -28,6 +28,9 @@ ROLLOUT_TERMINATE = 1
 ROLLOUT_STOP_AT_TARGET = 2
 OPT_ROLLOUT_SCHEDULE, OPT_ROLLOUT_EXTRA_WORKGROUPS, OPT_STREAM_ROWS, OPT_MLP_ARITHMETIC, OPT_TRAIN_KERNEL = 0, 1, 2, 3, 4
 OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE = 0, -1, -2, -3, -4
+CODE_STREAMING = 0
+_HEADS = {"pd": 0, "soft": 1}
+_ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sin": ACT_SIN}
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 _LIB_PATH = os.environ.get("HJBX_LIBRARY") or os.path.join(_CSRC, "libhjbx.so")   # (HJBX_LIBRARY: development builds of tools/dev)
@@ -45,10 +48,10 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=0",), "hjbx_softpd_relu.o"),    # soft-PD network: once per activation, like hjbx_mlp.hip
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=1",), "hjbx_softpd_tanh.o"),
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=2",), "hjbx_softpd_sin.o"),
-          ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds three headers as text for hiprtc (.incbin)
+          ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds the device headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
 _HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
-            "hjbx_user_kernels.hpp", os.path.join("..", "..", "include", "hjbx.h"))
+            "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
 class HjbxAdamState(C.Structure):
@@ -242,7 +245,7 @@ def _typed_signatures():
 
 EXPORTED_SYMBOLS = (
     ["hjbx_version", "hjbx_last_error", "hjbx_device_count", "hjbx_set_option", "hjbx_system_create", "hjbx_system_create_from_source",
-     "hjbx_last_compile_log", "hjbx_system_destroy", "hjbx_dims",
+     "hjbx_last_compile_log", "hjbx_system_enable_matrix_cores", "hjbx_system_matrix_cores", "hjbx_system_code_object", "hjbx_system_destroy", "hjbx_dims",
      "hjbx_reduce_workspace_bytes", "hjbx_rollout_workspace_bytes", "hjbx_value_grad_f32", "hjbx_vhjb_rollout_f32",
      "hjbx_value_loss_grad_workspace_bytes", "hjbx_value_loss_grad_f32", "hjbx_mix_gradients_f32", "hjbx_mix_adam_f32", "hjbx_replay_gather_f32",
      "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32", "hjbx_softpd_value_grad_f32", "hjbx_softpd_rollout_f32",
@@ -282,6 +285,12 @@ def lib() -> C.CDLL:
         L.hjbx_system_create_from_source.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_int, C.POINTER(_VP)]
         L.hjbx_last_compile_log.restype = C.c_size_t
         L.hjbx_last_compile_log.argtypes = [C.c_char_p, C.c_size_t]
+        L.hjbx_system_enable_matrix_cores.restype = C.c_int
+        L.hjbx_system_enable_matrix_cores.argtypes = [_VP]
+        L.hjbx_system_matrix_cores.restype = C.c_int
+        L.hjbx_system_matrix_cores.argtypes = [_VP]
+        L.hjbx_system_code_object.restype = C.c_size_t
+        L.hjbx_system_code_object.argtypes = [_VP, C.c_int, _VP, C.c_size_t]
         L.hjbx_system_destroy.restype = None
         L.hjbx_system_destroy.argtypes = [_VP]
         L.hjbx_dims.restype = C.c_int
@@ -350,7 +359,8 @@ def last_error() -> str:
 
 
 def compile_log() -> str:
-    """The hiprtc log of the calling thread's last hjbx_system_create_from_source."""
+    """The hiprtc log of the calling thread's last run-time compile (hjbx_system_create_from_source, or the matrix-core kernels of a user
+    system at their first use)."""
     n = lib().hjbx_last_compile_log(None, 0)
     buf = C.create_string_buffer(n + 1)
     lib().hjbx_last_compile_log(buf, n + 1)
@@ -402,6 +412,39 @@ class SystemHandle:
         check(rc)
         self._h = h
         return self
+
+    def enable_matrix_cores(self):
+        """hjbx_system_enable_matrix_cores: a user-defined system asks for the two persistent matrix-core kernels (value gradient, fused
+        rollout); they are compiled at the first call that needs them, once per (head, activation).  NotImplementedError with the
+        library's reason when the kernels cannot take this system (odd state dimension), ValueError for a built-in handle."""
+        check(lib().hjbx_system_enable_matrix_cores(self._h))
+
+    @property
+    def matrix_cores(self) -> bool:
+        """True for a user-defined system whose matrix-core kernels are enabled (built-in systems have theirs in the library: False)."""
+        return bool(lib().hjbx_system_matrix_cores(self._h))
+
+    def code_object(self, which="streaming") -> bytes:
+        """hjbx_system_code_object: the gfx950 ELF this user-defined system runs.  which = "streaming" (compiled at creation) or
+        (head, activation) with head in ("pd", "soft") and activation in ("relu", "tanh", "sin"): the matrix-core unit, compiled now if
+        it has not been.  NotImplementedError when the handle has not enabled the matrix-core kernels or the library refuses to ship the
+        unit, ValueError (with the compiler's log) when the source does not compile there."""
+        if which == "streaming":
+            code = CODE_STREAMING
+        else:
+            head, act = which
+            code = 1 + 3 * _HEADS[head] + _ACTIVATIONS[act]
+        size = lib().hjbx_system_code_object(self._h, code, None, 0)
+        if size == 0:
+            msg = last_error()
+            if "does not compile" in msg:
+                raise ValueError(f"hjbx: {msg}\n--- compiler log ---\n{compile_log()}")
+            if "not a user-defined" in msg or "unknown code object" in msg:
+                raise ValueError(f"hjbx: {msg}")
+            raise NotImplementedError(f"hjbx: {msg}")
+        buf = C.create_string_buffer(size)
+        lib().hjbx_system_code_object(self._h, code, buf, size)
+        return buf.raw
 
     @property
     def ptr(self):

@@ -435,10 +435,11 @@ class VHJBController(Controller):
                 dynamics, config.features, config.normalization_mean, config.normalization_std, self.xf, config.epsilon_scalar,
                 config.using_batch_norm, dtype=dtype, device=self.device, generator=self._init_gen, activation=activation)
         # activation: "relu" = controller/vhjb.py; "tanh" / "sin" = the notebooks' networks
-        # the matrix-core kernels carry the five built-in systems; a user-defined system (Dynamics.device_source) runs the value network
-        # through PyTorch and its own run-time compiled step / residual kernels
+        # the matrix-core kernels carry the five built-in systems, and a user-defined system (Dynamics.device_source) that asked for
+        # them (matrix_cores=True: value gradient and fused rollout compiled at first use); any other user system runs the value network
+        # through PyTorch and its own run-time compiled step / residual kernels.  The parameter gradient of a user system always does.
         builtin = dynamics.system.kind != _abi.SYS_USER
-        fusable = activation in ValueFunctionApproximator.FUSED_ACTIVATIONS and builtin
+        fusable = activation in ValueFunctionApproximator.FUSED_ACTIVATIONS and (builtin or dynamics.system.matrix_cores)
         self.fused_value_grad = (dtype == torch.float32 and fusable) if fused_value_grad is None else bool(fused_value_grad)
         if self.fused_value_grad and not fusable:
             raise NotImplementedError(f"no fused value-gradient kernel for the {activation} activation")

@@ -40,6 +40,7 @@
 #include "hjbx_mlp_x3.hpp"
 #include "hjbx_mlp_h2.hpp"
 #include "hjbx_mlp_kernels.hpp"
+#include "hjbx_mlp_host.hpp"
 
 using namespace hjbx;
 
@@ -91,20 +92,25 @@ static int check_activation(const hjbx_mlp* mlp, const char* who) {
     if (mlp->activation == HJBX_ACT_RELU || mlp->activation == HJBX_ACT_TANH || mlp->activation == HJBX_ACT_SIN) return HJBX_OK;
     return hjbx_set_error(HJBX_EINVAL, "%s: unknown activation %d", who, mlp->activation);
 }
+// a user-defined system that asked for the matrix-core kernels (hjbx_system_enable_matrix_cores) gets them compiled at run time, in the
+// float32 MFMA arithmetic only
+static int check_user_arithmetic(const char* who) {
+    if (hjbx_option_value(HJBX_OPT_MLP_ARITHMETIC) == 0) return HJBX_OK;
+    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: HJBX_OPT_MLP_ARITHMETIC=%d (split-operand MFMA) is not compiled for user-defined systems; set it to 0", who,
+                          hjbx_option_value(HJBX_OPT_MLP_ARITHMETIC));
+}
+static hjbx_user_net user_net(const hjbx_mlp* mlp) {
+    return hjbx_user_net{0, mlp->activation, mlp->mean, mlp->std, mlp->xf, mlp->eps_scalar, (const float*)mlp->W1, (const float*)mlp->W2,
+                         (const float*)mlp->W3, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
 #endif
 
 template <typename S> static int launch_value_grad(S sys, const hjbx_mlp* mlp, const float* x, float* V, float* g, int64_t B, void* st) {
     constexpr int N = S::N;
     constexpr int TL = HJBX_MLP_TL, WAVES = HJBX_MLP_WAVES;
-    MlpP<N> p;
-    for (int k = 0; k < N; ++k) { p.mean[k] = (float)mlp->mean[k]; p.istd[k] = (float)(1.0 / mlp->std[k]); p.xf[k] = (float)mlp->xf[k]; }
-    p.eps_s = (float)mlp->eps_scalar;
-    const int64_t ngroups = (B + 32 * TL - 1) / (32 * TL);
-    const int n_cu = hjbx_device_cus();
-    if (n_cu <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_value_grad_f32: no HIP device");
-    // one resident workgroup per CU (106 KB of LDS each); small batches are spread one tile group per CU
-    // rather than packed eight to a workgroup, so up to n_cu matrix pipes work on them
-    int64_t grid = ngroups < n_cu ? ngroups : n_cu;
+    const MlpP<N> p = make_mlp_params<N>(mlp->mean, mlp->std, mlp->xf, mlp->eps_scalar);
+    int64_t ngroups = 0, grid = 0;   // one resident workgroup per CU, small batches one tile group per CU (hjbx_mlp_host.hpp)
+    if (int rc = mlp_value_grad_grid(B, TL, &ngroups, &grid, "hjbx_value_grad_f32")) return rc;
     hipLaunchKernelGGL((k_value_grad_mfma<S, TL, WAVES, kAct, kArith>), dim3((unsigned)grid), dim3(WAVES * 64), 0, (hipStream_t)st, sys, p,
                        (const float*)mlp->W1, (const float*)mlp->W2, (const float*)mlp->W3, x, V, g, B, ngroups, MlpHeadPd{});
     hipError_t e = hipGetLastError();
@@ -157,6 +163,11 @@ extern "C" int hjbx_value_grad_f32(const hjbx_system* sys, const hjbx_mlp* mlp, 
         return hjbx_set_error(HJBX_EINVAL, "hjbx_value_grad_f32: x / gradV must be aligned to their row vector width");
     for (int k = 0; k < sys->n; ++k)
         if (!(mlp->std[k] != 0.0)) return hjbx_set_error(HJBX_EINVAL, "hjbx_value_grad_f32: normalization_std[%d] is zero", k);
+    if (hjbx_user_matrix_cores(sys)) {
+        if (int rc = check_user_arithmetic("hjbx_value_grad_f32")) return rc;
+        const hjbx_user_net net = user_net(mlp);
+        return hjbx_user_value_grad(sys, &net, x, V, g, B, stream, "hjbx_value_grad_f32");
+    }
     if (mlp->activation == HJBX_ACT_TANH) return hjbx_mlp_value_grad_act1(sys, mlp, x, V, g, B, stream);
     if (mlp->activation == HJBX_ACT_SIN) return hjbx_mlp_value_grad_act4(sys, mlp, x, V, g, B, stream);
     const int arith = hjbx_option_value(HJBX_OPT_MLP_ARITHMETIC);
@@ -172,19 +183,13 @@ static int launch_vhjb_rollout(const hjbx_system* sysh, S sys, const hjbx_task* 
                                int32_t* done_step, float* x_out, const int32_t* order, int64_t B, void* workspace, void* st) {
     constexpr int N = S::N, M = S::M;
     constexpr int WAVES = HJBX_MLP_WAVES;
-    MlpP<N> p;
-    for (int k = 0; k < N; ++k) { p.mean[k] = (float)mlp->mean[k]; p.istd[k] = (float)(1.0 / mlp->std[k]); p.xf[k] = (float)mlp->xf[k]; }
-    p.eps_s = (float)mlp->eps_scalar;
+    const MlpP<N> p = make_mlp_params<N>(mlp->mean, mlp->std, mlp->xf, mlp->eps_scalar);
     const auto tk = make_task<float, N, M>(task);
     const auto lim = make_limits<float, M>(sysh);
     RolloutOut<N, M> o{traj, u_log, cost, done, resid, done_step, x_out};
-    const int64_t ngroups = (B + 31) / 32;
-    const int n_cu = hjbx_device_cus();
-    if (n_cu <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_vhjb_rollout_f32: no HIP device");
-    int64_t grid = ngroups < n_cu ? ngroups : n_cu;  // as in launch_value_grad
-    const int sched = hjbx_option_value(HJBX_OPT_ROLLOUT_SCHEDULE);
-    grid += hjbx_option_value(HJBX_OPT_ROLLOUT_EXTRA_WORKGROUPS);   // test hook: workgroups that cannot be resident before others finish
-    if (grid > kMaxGrid) grid = kMaxGrid;
+    int64_t ngroups = 0, grid = 0;   // as in launch_value_grad, plus the schedule and the test hook (hjbx_mlp_host.hpp)
+    int sched = 0;
+    if (int rc = mlp_rollout_grid(B, &ngroups, &grid, &sched, "hjbx_vhjb_rollout_f32")) return rc;
     const float *W1 = (const float*)mlp->W1, *W2 = (const float*)mlp->W2, *W3 = (const float*)mlp->W3;
     auto launch = [&](auto integ) {
         hipLaunchKernelGGL((k_vhjb_rollout_mfma<decltype(integ)::value, S, WAVES, kAct, kArith>), dim3((unsigned)grid), dim3(WAVES * 64), 0,
@@ -258,6 +263,12 @@ extern "C" int hjbx_vhjb_rollout_f32(const hjbx_system* sys, const hjbx_task* ta
         return hjbx_set_error(HJBX_EINVAL, "hjbx_vhjb_rollout_f32: x / traj / x_out / u_log must be aligned to their row vector width");
     for (int k = 0; k < sys->n; ++k)
         if (!(mlp->std[k] != 0.0)) return hjbx_set_error(HJBX_EINVAL, "hjbx_vhjb_rollout_f32: normalization_std[%d] is zero", k);
+    if (hjbx_user_matrix_cores(sys)) {
+        if (int rc = check_user_arithmetic("hjbx_vhjb_rollout_f32")) return rc;
+        const hjbx_user_net net = user_net(mlp);
+        return hjbx_user_rollout(sys, task, &net, integrator, t_first, n_steps, T_max, x, traj, u_log, cost, done, resid, done_step, x_out, env_order, B,
+                                 workspace, stream, "hjbx_vhjb_rollout_f32");
+    }
     if (mlp->activation == HJBX_ACT_TANH)
         return hjbx_mlp_rollout_act1(sys, task, mlp, integrator, t_first, n_steps, T_max, x, traj, u_log, cost, done, resid, done_step, x_out, env_order, B, workspace, stream);
     if (mlp->activation == HJBX_ACT_SIN)

@@ -16,6 +16,7 @@
 #include "hjbx_systems.hpp"
 #include "hjbx_host.hpp"
 #include "hjbx_mlp_kernels.hpp"
+#include "hjbx_mlp_host.hpp"
 
 using namespace hjbx;
 
@@ -42,10 +43,7 @@ HJBX_HIDDEN int hjbx_softpd_rollout_act1(HJBX_SOFTPD_RO_ARGS);
 HJBX_HIDDEN int hjbx_softpd_rollout_act2(HJBX_SOFTPD_RO_ARGS);
 
 template <int N> static MlpP<N> softpd_params(const hjbx_softpd_mlp* mlp) {
-    MlpP<N> p;
-    for (int k = 0; k < N; ++k) { p.mean[k] = (float)mlp->mean[k]; p.istd[k] = (float)(1.0 / mlp->std[k]); p.xf[k] = (float)mlp->xf[k]; }
-    p.eps_s = 0.f;   // (no eps |e|^2 term in this network)
-    return p;
+    return make_mlp_params<N>(mlp->mean, mlp->std, mlp->xf, 0.0);   // (no eps |e|^2 term in this network)
 }
 
 static MlpHeadSoft softpd_head(const hjbx_softpd_mlp* mlp) {
@@ -55,10 +53,8 @@ static MlpHeadSoft softpd_head(const hjbx_softpd_mlp* mlp) {
 template <typename S>
 static int launch_softpd_value_grad(S sys, const hjbx_softpd_mlp* mlp, const float* x, float* V, float* g, int64_t B, void* st) {
     constexpr int N = S::N;
-    const int64_t ngroups = (B + 31) / 32;
-    const int n_cu = hjbx_device_cus();
-    if (n_cu <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_softpd_value_grad_f32: no HIP device");
-    const int64_t grid = ngroups < n_cu ? ngroups : n_cu;
+    int64_t ngroups = 0, grid = 0;
+    if (int rc = mlp_value_grad_grid(B, 1, &ngroups, &grid, "hjbx_softpd_value_grad_f32")) return rc;
     hipLaunchKernelGGL((k_value_grad_mfma<S, 1, kWaves, kAct, 0, MlpHeadSoft>), dim3((unsigned)grid), dim3(kWaves * 64), 0, (hipStream_t)st, sys,
                        softpd_params<N>(mlp), (const float*)mlp->W1, (const float*)mlp->W2, (const float*)mlp->W3, x, V, g, B, ngroups,
                        softpd_head(mlp));
@@ -93,13 +89,9 @@ static int launch_softpd_rollout(const hjbx_system* sysh, S sys, const hjbx_task
     const auto tk = make_task<float, N, M>(task);
     const auto lim = make_limits<float, M>(sysh);
     RolloutOut<N, M> o{traj, u_log, cost, done, resid, done_step, x_out};
-    const int64_t ngroups = (B + 31) / 32;
-    const int n_cu = hjbx_device_cus();
-    if (n_cu <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_softpd_rollout_f32: no HIP device");
-    int64_t grid = ngroups < n_cu ? ngroups : n_cu;   // as hjbx_vhjb_rollout_f32, schedule and test hook included
-    const int sched = hjbx_option_value(HJBX_OPT_ROLLOUT_SCHEDULE);
-    grid += hjbx_option_value(HJBX_OPT_ROLLOUT_EXTRA_WORKGROUPS);
-    if (grid > kMaxGrid) grid = kMaxGrid;
+    int64_t ngroups = 0, grid = 0;   // as hjbx_vhjb_rollout_f32, schedule and test hook included
+    int sched = 0;
+    if (int rc = mlp_rollout_grid(B, &ngroups, &grid, &sched, "hjbx_softpd_rollout_f32")) return rc;
     const float *W1 = (const float*)mlp->W1, *W2 = (const float*)mlp->W2, *W3 = (const float*)mlp->W3;
     auto launch = [&](auto integ) {
         hipLaunchKernelGGL((k_vhjb_rollout_mfma<decltype(integ)::value, S, kWaves, kAct, 0, MlpHeadSoft>), dim3((unsigned)grid), dim3(kWaves * 64), 0,
@@ -130,11 +122,17 @@ int HJBX_SOFTPD_SYM(hjbx_softpd_rollout_act)(const hjbx_system* sys, const hjbx_
 }
 
 #if HJBX_SOFTPD_ACT == 0
-// the checks both entry points share: descriptor, features, activation, normalisation, and the handle (built-in systems only)
+static hjbx_user_net user_net(const hjbx_softpd_mlp* mlp) {
+    return hjbx_user_net{1, mlp->activation, mlp->mean, mlp->std, mlp->xf, 0.0, (const float*)mlp->W1, (const float*)mlp->W2, (const float*)mlp->W3,
+                         (const float*)mlp->b1, (const float*)mlp->b2, (const float*)mlp->b3, (const float*)mlp->w4, (const float*)mlp->b4};
+}
+
+// the checks both entry points share: descriptor, features, activation, normalisation, and the handle (built-in systems, and user-defined
+// ones that asked for the matrix-core kernels: hjbx_system_enable_matrix_cores)
 static int check_softpd(const hjbx_system* sys, const hjbx_softpd_mlp* mlp, const char* who) {
     if (!mlp->W1 || !mlp->b1 || !mlp->W2 || !mlp->b2 || !mlp->W3 || !mlp->b3 || !mlp->w4 || !mlp->b4)
         return hjbx_set_error(HJBX_EINVAL, "%s: NULL weight or bias pointer", who);
-    if (sys->kind == HJBX_SYS_USER)
+    if (sys->kind == HJBX_SYS_USER && !hjbx_user_matrix_cores(sys))
         return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the matrix-core kernels exist for the built-in systems only", who);
     if (mlp->h1 != kH1 || mlp->h2 != kH2 || mlp->h3 != kH3)
         return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: features must be [128,128,64], got [%d,%d,%d]", who, mlp->h1, mlp->h2, mlp->h3);
@@ -156,6 +154,10 @@ extern "C" int hjbx_softpd_value_grad_f32(const hjbx_system* sys, const hjbx_sof
     const uintptr_t am = (row % 16 == 0) ? 15u : 7u;
     if ((reinterpret_cast<uintptr_t>(x) & am) || (g && (reinterpret_cast<uintptr_t>(g) & am)))
         return hjbx_set_error(HJBX_EINVAL, "hjbx_softpd_value_grad_f32: x / gradV must be aligned to their row vector width");
+    if (sys->kind == HJBX_SYS_USER) {
+        const hjbx_user_net net = user_net(mlp);
+        return hjbx_user_value_grad(sys, &net, x, V, g, B, stream, "hjbx_softpd_value_grad_f32");
+    }
     auto* fn = mlp->activation == HJBX_ACT_TANH ? hjbx_softpd_value_grad_act1 : mlp->activation == HJBX_ACT_SIN ? hjbx_softpd_value_grad_act2
                                                                                                                : hjbx_softpd_value_grad_act0;
     return fn(sys, mlp, x, V, g, B, stream);
@@ -181,6 +183,11 @@ extern "C" int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* 
     if ((reinterpret_cast<uintptr_t>(x) & am) || (traj && (reinterpret_cast<uintptr_t>(traj) & am)) ||
         (x_out && (reinterpret_cast<uintptr_t>(x_out) & am)) || (u_log && (reinterpret_cast<uintptr_t>(u_log) & um)))
         return hjbx_set_error(HJBX_EINVAL, "hjbx_softpd_rollout_f32: x / traj / x_out / u_log must be aligned to their row vector width");
+    if (sys->kind == HJBX_SYS_USER) {
+        const hjbx_user_net net = user_net(mlp);
+        return hjbx_user_rollout(sys, task, &net, integrator, t_first, n_steps, T_max, x, traj, u_log, cost, done, resid, done_step, x_out, env_order, B,
+                                 workspace, stream, "hjbx_softpd_rollout_f32");
+    }
     auto* fn = mlp->activation == HJBX_ACT_TANH ? hjbx_softpd_rollout_act1 : mlp->activation == HJBX_ACT_SIN ? hjbx_softpd_rollout_act2
                                                                                                             : hjbx_softpd_rollout_act0;
     return fn(sys, task, mlp, integrator, t_first, n_steps, T_max, x, traj, u_log, cost, done, resid, done_step, x_out, env_order, B, workspace, stream);

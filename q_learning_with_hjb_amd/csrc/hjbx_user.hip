@@ -1,8 +1,13 @@
 // hjbx_user.hip -- user-defined systems: the open half of the reference's plugin surface (dynamics/dynamics_basic.py:64-94: any subclass may
 // define get_M / get_C / get_G / get_B, or get_control_affine_matrix itself).  hjbx_system_create_from_source compiles the subclass's
 // device-code snippet with hiprtc into the library's own streaming kernels (hjbx_user_kernels.hpp + hjbx_stream_kernels.hpp, embedded
-// below as text), keeps the code object in the handle, and the entry points of hjbx_kernels.hip launch it through the module API.  The
-// MFMA entry points (value network, fused rollout, parameter gradient) exist for the built-in systems only.
+// below as text), keeps the code object in the handle, and the entry points of hjbx_kernels.hip launch it through the module API.
+//
+// A handle that asked for it (hjbx_system_enable_matrix_cores) also gets the two persistent matrix-core kernels of the value network
+// (controller/vhjb.py:17-60, 162-193, 201-202: network, its input gradient, the closed loop): a second translation unit,
+// hjbx_user_mlp_kernels.hpp, compiled at the first call for each (head, activation) and kept in the handle; hjbx_mlp.hip and
+// hjbx_softpd.hip hand an enabled user handle over to hjbx_user_value_grad / hjbx_user_rollout below.  The parameter gradient
+// (hjbx_value_loss_grad_f32) stays with the built-in systems.
 //
 // hiprtc is opened with dlopen at first use: libhjbx.so has no link-time dependency on it, and a process that never creates a user system
 // never loads it.  Compilation needs no GPU (the CPU test compiles a snippet); modules are loaded per device at the first launch.
@@ -10,6 +15,7 @@
 #include <hip/hiprtc.h>
 
 #include <dlfcn.h>
+#include <elf.h>
 
 #include <cstdio>
 #include <cstring>
@@ -21,6 +27,8 @@
 
 #include "hjbx_internal.hpp"
 #include "hjbx_host.hpp"
+#include "hjbx_mlp_kernels.hpp"   // host side: the by-value argument structs of the two matrix-core kernels, exactly as the device unit sees them
+#include "hjbx_mlp_host.hpp"
 
 // ---- the header texts handed to hiprtc, embedded at build time (host pass only) ------------------------------------------------------
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -33,17 +41,43 @@
 HJBX_EMBED(hjbx_src_systems, "hjbx_systems.hpp");
 HJBX_EMBED(hjbx_src_stream, "hjbx_stream_kernels.hpp");
 HJBX_EMBED(hjbx_src_user, "hjbx_user_kernels.hpp");
+HJBX_EMBED(hjbx_src_user_mlp, "hjbx_user_mlp_kernels.hpp");
+HJBX_EMBED(hjbx_src_mlp_core, "hjbx_mlp_core.hpp");
+HJBX_EMBED(hjbx_src_mlp_kernels, "hjbx_mlp_kernels.hpp");
+HJBX_EMBED(hjbx_src_mlp_x3, "hjbx_mlp_x3.hpp");
+HJBX_EMBED(hjbx_src_mlp_h2, "hjbx_mlp_h2.hpp");
+HJBX_EMBED(hjbx_src_abi, "../../include/hjbx.h");
 #endif
 extern "C" const char hjbx_src_systems[];
 extern "C" const char hjbx_src_stream[];
 extern "C" const char hjbx_src_user[];
+extern "C" const char hjbx_src_user_mlp[];
+extern "C" const char hjbx_src_mlp_core[];
+extern "C" const char hjbx_src_mlp_kernels[];
+extern "C" const char hjbx_src_mlp_x3[];
+extern "C" const char hjbx_src_mlp_h2[];
+extern "C" const char hjbx_src_abi[];
 
-// what hiprtc's built-in runtime header does not bring: the two system headers the library's own headers include
+// what hiprtc's built-in runtime header does not bring: the system headers the library's own headers include, as far as they use them
 static const char kStubRuntime[] = "// hip/hip_runtime.h: provided by hiprtc itself\n";
 static const char kStubStdint[] =
     "#pragma once\n"
     "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
     "typedef int int32_t; typedef unsigned int uint32_t; typedef long int64_t; typedef unsigned long uint64_t; typedef unsigned long uintptr_t;\n";
+static const char kStubStddef[] =
+    "#pragma once\n"
+    "typedef unsigned long size_t;\n"
+    "#ifndef offsetof\n#define offsetof(t, m) __builtin_offsetof(t, m)\n#endif\n";
+static const char kStubTypeTraits[] =
+    "#pragma once\n"
+    "namespace std {\n"
+    "template <bool C, class A, class B> struct conditional { using type = A; };\n"
+    "template <class A, class B> struct conditional<false, A, B> { using type = B; };\n"
+    "template <bool C, class A, class B> using conditional_t = typename conditional<C, A, B>::type;\n"
+    "template <class T, T v> struct integral_constant { static constexpr T value = v; };\n"
+    "}\n";
+// hjbx_internal.hpp of the device units: the ABI's enums and constants, none of the host-side declarations
+static const char kStubInternal[] = "#pragma once\n#include \"hjbx.h\"\n";
 
 // ---- hiprtc through dlopen -----------------------------------------------------------------------------------------------------
 namespace {
@@ -55,6 +89,8 @@ struct Rtc {
     decltype(&hiprtcGetCodeSize) code_size = nullptr;
     decltype(&hiprtcGetCode) code = nullptr;
     decltype(&hiprtcDestroyProgram) destroy = nullptr;
+    decltype(&hiprtcAddNameExpression) add_name = nullptr;
+    decltype(&hiprtcGetLoweredName) lowered = nullptr;
     bool ok = false;
 };
 
@@ -71,21 +107,189 @@ const Rtc& rtc() {
 #define HJBX_SYM(field, sym) r.field = reinterpret_cast<decltype(r.field)>(dlsym(h, #sym))
         HJBX_SYM(create, hiprtcCreateProgram); HJBX_SYM(compile, hiprtcCompileProgram); HJBX_SYM(log_size, hiprtcGetProgramLogSize);
         HJBX_SYM(log, hiprtcGetProgramLog); HJBX_SYM(code_size, hiprtcGetCodeSize); HJBX_SYM(code, hiprtcGetCode);
-        HJBX_SYM(destroy, hiprtcDestroyProgram);
+        HJBX_SYM(destroy, hiprtcDestroyProgram); HJBX_SYM(add_name, hiprtcAddNameExpression); HJBX_SYM(lowered, hiprtcGetLoweredName);
 #undef HJBX_SYM
-        r.ok = r.create && r.compile && r.log_size && r.log && r.code_size && r.code && r.destroy;
+        r.ok = r.create && r.compile && r.log_size && r.log && r.code_size && r.code && r.destroy && r.add_name && r.lowered;
     });
     return r;
 }
 
 thread_local std::string g_compile_log;
 
-struct UserProgram {
+// one code object of a handle and what has been loaded from it, per device
+struct UserUnit {
     std::vector<char> code;                          // the gfx950 code object
-    std::mutex mu;
     hipModule_t mod[kMaxDevices] = {};
     std::map<std::string, hipFunction_t> fn[kMaxDevices];
+    // a matrix-core unit only: 0 = not compiled yet, 1 = ready, -1 = the compile was refused (status, message and compiler log kept: a
+    // second call reports them again instead of compiling for another 20 s)
+    int state = 0, status = HJBX_OK;
+    std::string error, log;
+    std::string kernel[3];                           // symbols of: value gradient, Euler rollout, RK4 rollout
 };
+
+struct UserProgram {
+    std::mutex mu;                                   // guards the module / function caches of every unit
+    UserUnit stream;                                 // the streaming kernels (compiled at creation)
+    // what the handle was created with: the matrix-core units are compiled from the same text and -D values, later
+    std::string source;
+    int user_kind = 0, n = 0, m = 0, np = 1;
+    std::mutex mc_mu;                                // guards `matrix_cores` and the state of mc[][] (held across a lazy compile)
+    bool matrix_cores = false;                       // hjbx_system_enable_matrix_cores
+    UserUnit mc[2][3];                               // [head: 0 PD, 1 soft-PD][hjbx_activation]
+};
+
+// Compile `top` (one #include line) for the user's snippet with the library's own flags + `extra`; name expressions are resolved into
+// out->kernel[].  Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
+int compile_unit(const Rtc& R, const char* who, const char* top, const char* unit_name, const std::string& snippet, int user_kind, int n, int m,
+                 int np, const std::vector<std::string>& extra, const std::vector<const char*>& name_exprs, UserUnit* out) {
+    const char* headers[] = {hjbx_src_systems, hjbx_src_stream, hjbx_src_user, hjbx_src_user_mlp, hjbx_src_mlp_core, hjbx_src_mlp_kernels,
+                             hjbx_src_mlp_x3, hjbx_src_mlp_h2, hjbx_src_abi, kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint,
+                             kStubStddef, kStubStddef, kStubTypeTraits};
+    const char* names[] = {"hjbx_systems.hpp", "hjbx_stream_kernels.hpp", "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_core.hpp",
+                           "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx.h", "hjbx_internal.hpp", "hjbx_user_snippet.hpp",
+                           "hip/hip_runtime.h", "stdint.h", "stddef.h", "cstddef", "type_traits"};
+    static_assert(sizeof(headers) == sizeof(names), "one name per header");
+    hiprtcProgram prog = nullptr;
+    if (R.create(&prog, top, unit_name, (int)(sizeof(headers) / sizeof(headers[0])), headers, names) != HIPRTC_SUCCESS)
+        return hjbx_set_error(HJBX_EHIP, "%s: hiprtcCreateProgram failed", who);
+    for (const char* e : name_exprs)
+        if (R.add_name(prog, e) != HIPRTC_SUCCESS) { R.destroy(&prog); return hjbx_set_error(HJBX_EHIP, "%s: hiprtcAddNameExpression(%s) failed", who, e); }
+    // the flags of the library's own build: -ffp-contract=on keeps a user system's fused rollout bit-identical to its step kernels
+    std::vector<std::string> o = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-DHJBX_USER_N=" + std::to_string(n),
+                                  "-DHJBX_USER_M=" + std::to_string(m), "-DHJBX_USER_NP=" + std::to_string(np),
+                                  "-DHJBX_USER_KIND=" + std::to_string(user_kind)};
+    o.insert(o.end(), extra.begin(), extra.end());
+    std::vector<const char*> opts;
+    for (const std::string& f : o) opts.push_back(f.c_str());
+    const hiprtcResult rc = R.compile(prog, (int)opts.size(), opts.data());
+    size_t ls = 0;
+    if (R.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+        g_compile_log.resize(ls);
+        if (R.log(prog, &g_compile_log[0]) != HIPRTC_SUCCESS) g_compile_log.clear();
+    }
+    if (rc != HIPRTC_SUCCESS) {
+        R.destroy(&prog);
+        return hjbx_set_error(HJBX_EINVAL, "%s: the device source does not compile (hjbx_last_compile_log has the compiler's messages): %.300s", who,
+                              g_compile_log.c_str());
+    }
+    size_t cs = 0;
+    if (R.code_size(prog, &cs) != HIPRTC_SUCCESS || cs == 0) { R.destroy(&prog); return hjbx_set_error(HJBX_EHIP, "%s: no code object", who); }
+    out->code.resize(cs);
+    hiprtcResult rg = R.code(prog, out->code.data());
+    for (size_t i = 0; rg == HIPRTC_SUCCESS && i < name_exprs.size() && i < 3; ++i) {
+        const char* low = nullptr;
+        rg = R.lowered(prog, name_exprs[i], &low);
+        if (rg == HIPRTC_SUCCESS && low) out->kernel[i] = low;
+    }
+    R.destroy(&prog);
+    if (rg != HIPRTC_SUCCESS) { out->code.clear(); return hjbx_set_error(HJBX_EHIP, "%s: hiprtcGetCode / hiprtcGetLoweredName failed", who); }
+    return HJBX_OK;
+}
+
+// PRIVATE_SEGMENT_FIXED_SIZE (bytes 4..7 of the kernel descriptor, symbol `<kernel>.kd`) of a kernel in an AMDGPU code object: the bytes
+// of scratch per work-item, i.e. whether the register allocator spilled VGPRs.  -1 when the symbol is not found.
+long kernel_scratch_bytes(const std::vector<char>& code, const std::string& kernel) {
+    Elf64_Ehdr eh;
+    if (code.size() < sizeof eh) return -1;
+    memcpy(&eh, code.data(), sizeof eh);
+    if (memcmp(eh.e_ident, ELFMAG, SELFMAG) != 0 || eh.e_ident[EI_CLASS] != ELFCLASS64 || eh.e_shentsize != sizeof(Elf64_Shdr)) return -1;
+    if (eh.e_shoff > code.size() || (size_t)eh.e_shnum * sizeof(Elf64_Shdr) > code.size() - eh.e_shoff) return -1;
+    std::vector<Elf64_Shdr> sh(eh.e_shnum);
+    if (eh.e_shnum) memcpy(sh.data(), code.data() + eh.e_shoff, sh.size() * sizeof(Elf64_Shdr));
+    auto inside = [&](const Elf64_Shdr& s) { return s.sh_offset <= code.size() && s.sh_size <= code.size() - s.sh_offset; };
+    const std::string want = kernel + ".kd";
+    for (const Elf64_Shdr& st : sh) {
+        if ((st.sh_type != SHT_SYMTAB && st.sh_type != SHT_DYNSYM) || st.sh_link >= sh.size() || !inside(st) || !inside(sh[st.sh_link])) continue;
+        const Elf64_Shdr& str = sh[st.sh_link];
+        for (size_t k = 0; k + sizeof(Elf64_Sym) <= st.sh_size; k += sizeof(Elf64_Sym)) {
+            Elf64_Sym sym;
+            memcpy(&sym, code.data() + st.sh_offset + k, sizeof sym);
+            if (sym.st_name >= str.sh_size || sym.st_shndx >= sh.size()) continue;
+            const char* nm = code.data() + str.sh_offset + sym.st_name;
+            if (strnlen(nm, str.sh_size - sym.st_name) != want.size() || memcmp(nm, want.data(), want.size()) != 0) continue;
+            const Elf64_Shdr& sec = sh[sym.st_shndx];
+            if (!inside(sec) || sym.st_value < sec.sh_addr || sym.st_value - sec.sh_addr + 8 > sec.sh_size) return -1;
+            uint32_t priv = 0;
+            memcpy(&priv, code.data() + sec.sh_offset + (sym.st_value - sec.sh_addr) + 4, 4);
+            return (long)priv;
+        }
+    }
+    return -1;
+}
+
+// Launch `kernel` of `unit`: `grid` workgroups of `block` threads on `stream`; the module is loaded on the current device on first use.
+int launch_unit(UserProgram* u, UserUnit& unit, const char* kernel, unsigned grid, unsigned block, void** args, void* stream, const char* who) {
+    const int dev = hjbx_current_device();
+    if (dev < 0) return hjbx_set_error(HJBX_ENODEVICE, "%s: no HIP device", who);
+    hipFunction_t f = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(u->mu);
+        if (!unit.mod[dev]) {
+            const hipError_t e = hipModuleLoadData(&unit.mod[dev], unit.code.data());
+            if (e != hipSuccess) { unit.mod[dev] = nullptr; return hjbx_set_error(HJBX_EHIP, "hipModuleLoadData: %s", hipGetErrorString(e)); }
+        }
+        auto it = unit.fn[dev].find(kernel);
+        if (it == unit.fn[dev].end()) {
+            const hipError_t e = hipModuleGetFunction(&f, unit.mod[dev], kernel);
+            if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hipModuleGetFunction(%s): %s", kernel, hipGetErrorString(e));
+            unit.fn[dev][kernel] = f;
+        } else {
+            f = it->second;
+        }
+    }
+    const hipError_t e = hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+    if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "%s: %s", who, hipGetErrorString(e));
+    return HJBX_OK;
+}
+
+void unload_unit(UserUnit& unit) {
+    for (int d = 0; d < kMaxDevices; ++d)
+        if (unit.mod[d]) (void)hipModuleUnload(unit.mod[d]);
+}
+
+// The matrix-core unit of an enabled handle for (head, activation), compiled now if this is the first call that needs it.
+int matrix_core_unit(const hjbx_system* s, int soft, int act, const char* who, UserUnit** out) {
+    UserProgram* u = s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "%s: not a user-defined system", who);
+    if (soft < 0 || soft > 1 || act < 0 || act > 2) return hjbx_set_error(HJBX_EINVAL, "%s: unknown head %d / activation %d", who, soft, act);
+    std::lock_guard<std::mutex> lock(u->mc_mu);
+    if (!u->matrix_cores)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
+    UserUnit& unit = u->mc[soft][act];
+    if (unit.state == 0) {
+        g_compile_log.clear();
+        const Rtc& R = rtc();   // (loaded: the handle was created through it)
+        int rc = compile_unit(R, who, "#include \"hjbx_user_mlp_kernels.hpp\"\n", "hjbx_user_matrix_cores.hip", u->source, u->user_kind, u->n, u->m,
+                              u->np, {"-DHJBX_USER_MLP_ACT=" + std::to_string(act), "-DHJBX_USER_MLP_SOFT=" + std::to_string(soft)},
+                              {"HJBX_UM_VALUE_GRAD", "HJBX_UM_ROLLOUT_EULER", "HJBX_UM_ROLLOUT_RK4"}, &unit);
+        // Two waves per SIMD leave 256 registers per lane and the kernels keep a whole layer in them: a spill to scratch is a kernel that
+        // must not be launched (a spill store inside an EXEC-predicated region once produced wrong trajectories here)
+        for (int k = 0; rc == HJBX_OK && k < 3; ++k) {
+            const long scratch = kernel_scratch_bytes(unit.code, unit.kernel[k]);
+            if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, unit.kernel[k].c_str());
+            else if (scratch > 0)
+                rc = hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the %s kernel of this user system (n=%d m=%d, activation %d, %s head) needs %ld bytes of "
+                                    "scratch: its code does not fit the 256 registers of the matrix-core kernels", who,
+                                    k == 0 ? "value-gradient" : k == 1 ? "Euler rollout" : "RK4 rollout", u->n, u->m, act, soft ? "soft-PD" : "PD", scratch);
+        }
+        unit.state = rc == HJBX_OK ? 1 : -1;
+        unit.status = rc;
+        unit.log = g_compile_log;
+        if (rc != HJBX_OK) {
+            char msg[512];
+            hjbx_last_error(msg, sizeof msg);
+            unit.error = msg;
+            unit.code.clear();
+        }
+    }
+    if (unit.state < 0) {
+        g_compile_log = unit.log;
+        return hjbx_set_error(unit.status, "%s", unit.error.c_str());
+    }
+    *out = &unit;
+    return HJBX_OK;
+}
 }  // namespace
 
 extern "C" size_t hjbx_last_compile_log(char* buf, size_t buflen) {
@@ -101,8 +305,9 @@ extern "C" size_t hjbx_last_compile_log(char* buf, size_t buflen) {
 void hjbx_user_release(void* up) {
     UserProgram* u = static_cast<UserProgram*>(up);
     if (!u) return;
-    for (int d = 0; d < kMaxDevices; ++d)
-        if (u->mod[d]) (void)hipModuleUnload(u->mod[d]);
+    unload_unit(u->stream);
+    for (auto& head : u->mc)
+        for (UserUnit& unit : head) unload_unit(unit);
     delete u;
 }
 
@@ -125,42 +330,14 @@ extern "C" int hjbx_system_create_from_source(int user_kind, const char* device_
         const char* why = dlerror();       // (one call: dlerror clears the message it returns)
         return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_system_create_from_source: libhiprtc.so could not be loaded (%s)", why ? why : "symbols missing");
     }
-
-    const char* headers[] = {hjbx_src_systems, hjbx_src_stream, hjbx_src_user, device_source, kStubRuntime, kStubStdint};
-    const char* names[] = {"hjbx_systems.hpp", "hjbx_stream_kernels.hpp", "hjbx_user_kernels.hpp", "hjbx_user_snippet.hpp", "hip/hip_runtime.h", "stdint.h"};
-    hiprtcProgram prog = nullptr;
-    if (R.create(&prog, "#include \"hjbx_user_kernels.hpp\"\n", "hjbx_user_system.hip", 6, headers, names) != HIPRTC_SUCCESS)
-        return hjbx_set_error(HJBX_EHIP, "hiprtcCreateProgram failed");
-    char dn[32], dm[32], dp[32], dk[32];
-    snprintf(dn, sizeof dn, "-DHJBX_USER_N=%d", n);
-    snprintf(dm, sizeof dm, "-DHJBX_USER_M=%d", m);
-    snprintf(dp, sizeof dp, "-DHJBX_USER_NP=%d", n_params > 0 ? n_params : 1);
-    snprintf(dk, sizeof dk, "-DHJBX_USER_KIND=%d", user_kind);
-    // the flags of the library's own build: -ffp-contract=on keeps a user system's fused rollout bit-identical to its step kernels
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", dn, dm, dp, dk};
-    const hiprtcResult rc = R.compile(prog, 8, opts);
-    size_t ls = 0;
-    if (R.log_size(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-        g_compile_log.resize(ls);
-        if (R.log(prog, &g_compile_log[0]) != HIPRTC_SUCCESS) g_compile_log.clear();
-    }
-    if (rc != HIPRTC_SUCCESS) {
-        R.destroy(&prog);
-        return hjbx_set_error(HJBX_EINVAL, "hjbx_system_create_from_source: the device source does not compile (hjbx_last_compile_log has the "
-                                           "compiler's messages): %.300s", g_compile_log.c_str());
-    }
-    size_t cs = 0;
     UserProgram* u = new (std::nothrow) UserProgram();
-    if (!u || R.code_size(prog, &cs) != HIPRTC_SUCCESS || cs == 0) {
-        R.destroy(&prog);
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "out of host memory");
+    u->source = device_source; u->user_kind = user_kind; u->n = n; u->m = m; u->np = n_params > 0 ? n_params : 1;
+    if (int rc = compile_unit(R, "hjbx_system_create_from_source", "#include \"hjbx_user_kernels.hpp\"\n", "hjbx_user_system.hip", u->source, user_kind,
+                              n, m, u->np, {}, {}, &u->stream)) {
         delete u;
-        return hjbx_set_error(HJBX_EHIP, "hjbx_system_create_from_source: no code object");
+        return rc;
     }
-    u->code.resize(cs);
-    const hiprtcResult rg = R.code(prog, u->code.data());
-    R.destroy(&prog);
-    if (rg != HIPRTC_SUCCESS) { delete u; return hjbx_set_error(HJBX_EHIP, "hiprtcGetCode failed"); }
-
     hjbx_system* s = new (std::nothrow) hjbx_system();
     if (!s) { delete u; return hjbx_set_error(HJBX_EINVAL, "out of host memory"); }
     memset(s, 0, sizeof(*s));
@@ -172,30 +349,114 @@ extern "C" int hjbx_system_create_from_source(int user_kind, const char* device_
     return HJBX_OK;
 }
 
-// Launch `kernel` (an extern "C" name of hjbx_user_kernels.hpp) of this handle's code object: `grid` workgroups of 256 threads on `stream`,
-// args = pointers to the kernel's arguments in order (the first one a UserBlob).  The module is loaded on the current device on first use.
+extern "C" int hjbx_system_enable_matrix_cores(hjbx_system* sys) {
+    if (!sys) return hjbx_set_error(HJBX_EINVAL, "hjbx_system_enable_matrix_cores: system handle is NULL");
+    UserProgram* u = sys->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(sys->user) : nullptr;
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "hjbx_system_enable_matrix_cores: a built-in system has its matrix-core kernels already (user-defined systems only)");
+    if (sys->n % 2)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_system_enable_matrix_cores: the matrix-core kernels need an even state dimension (k-steps of 2), got n=%d", sys->n);
+    if (sys->n > HJBX_MAX_N || sys->m > HJBX_MAX_M)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_system_enable_matrix_cores: the matrix-core kernels take n<=%d, m<=%d", HJBX_MAX_N, HJBX_MAX_M);
+    std::lock_guard<std::mutex> lock(u->mc_mu);
+    u->matrix_cores = true;
+    return HJBX_OK;
+}
+
+bool hjbx_user_matrix_cores(const hjbx_system* s) {
+    UserProgram* u = s && s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
+    if (!u) return false;
+    std::lock_guard<std::mutex> lock(u->mc_mu);
+    return u->matrix_cores;
+}
+
+extern "C" int hjbx_system_matrix_cores(const hjbx_system* sys) { return hjbx_user_matrix_cores(sys) ? 1 : 0; }
+
+extern "C" size_t hjbx_system_code_object(const hjbx_system* sys, int which, void* buf, size_t len) {
+    UserProgram* u = sys && sys->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(sys->user) : nullptr;
+    if (!u) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: not a user-defined system"); return 0; }
+    const UserUnit* unit = &u->stream;
+    if (which != HJBX_CODE_STREAMING) {
+        if (which < 1 || which > 6) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: unknown code object %d", which); return 0; }
+        UserUnit* mc = nullptr;
+        if (matrix_core_unit(sys, (which - 1) / 3, (which - 1) % 3, "hjbx_system_code_object", &mc) != HJBX_OK) return 0;
+        unit = mc;
+    }
+    if (buf && len) memcpy(buf, unit->code.data(), len < unit->code.size() ? len : unit->code.size());
+    return unit->code.size();
+}
+
+// Launch `kernel` (an extern "C" name of hjbx_user_kernels.hpp) of this handle's streaming code object: `grid` workgroups of 256 threads on
+// `stream`, args = pointers to the kernel's arguments in order (the first one a UserBlob).
 int hjbx_user_launch(const hjbx_system* s, const char* kernel, unsigned grid, void** args, void* stream) {
     UserProgram* u = static_cast<UserProgram*>(s->user);
     if (!u) return hjbx_set_error(HJBX_EINVAL, "system handle has no user program");
-    const int dev = hjbx_current_device();
-    if (dev < 0) return hjbx_set_error(HJBX_ENODEVICE, "%s: no HIP device", kernel);
-    hipFunction_t f = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->mod[dev]) {
-            const hipError_t e = hipModuleLoadData(&u->mod[dev], u->code.data());
-            if (e != hipSuccess) { u->mod[dev] = nullptr; return hjbx_set_error(HJBX_EHIP, "hipModuleLoadData: %s", hipGetErrorString(e)); }
-        }
-        auto it = u->fn[dev].find(kernel);
-        if (it == u->fn[dev].end()) {
-            const hipError_t e = hipModuleGetFunction(&f, u->mod[dev], kernel);
-            if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hipModuleGetFunction(%s): %s", kernel, hipGetErrorString(e));
-            u->fn[dev][kernel] = f;
-        } else {
-            f = it->second;
-        }
-    }
-    const hipError_t e = hipModuleLaunchKernel(f, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-    if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "%s: %s", kernel, hipGetErrorString(e));
-    return HJBX_OK;
+    return launch_unit(u, u->stream, kernel, grid, 256, args, stream, kernel);
+}
+
+// ---- the matrix-core kernels of an enabled handle --------------------------------------------------------------------------------
+namespace {
+struct UserBlobF { float p[HJBX_USER_MAX_PARAMS]; };   // the kernels' first argument is `struct { float p[n_params]; }`
+UserBlobF user_blob(const hjbx_system* s) {
+    UserBlobF b;
+    for (int i = 0; i < HJBX_USER_MAX_PARAMS; ++i) b.p[i] = i < s->n_params ? (float)s->p[i] : 0.f;
+    return b;
+}
+MlpHeadSoft user_head(const hjbx_user_net* net) { return MlpHeadSoft{net->b1, net->b2, net->b3, net->w4, net->b4}; }
+constexpr unsigned kMcBlock = 8 * 64;   // WAVES * 64 of hjbx_user_mlp_kernels.hpp
+
+// calls f(integral_constant<int, n>, integral_constant<int, m>) for the (even) state and control dimension of an enabled handle
+template <typename F> int with_mc_dims(const hjbx_system* s, const char* who, F&& f) {
+#define HJBX_UD(NN)                                                                                   \
+    case NN:                                                                                          \
+        if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
+        if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
+        if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
+        break;
+    switch (s->n) { HJBX_UD(2) HJBX_UD(4) HJBX_UD(6) HJBX_UD(8) HJBX_UD(10) }
+#undef HJBX_UD
+    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no matrix-core kernel for a user system with n=%d m=%d", who, s->n, s->m);
+}
+}  // namespace
+
+int hjbx_user_value_grad(const hjbx_system* s, const hjbx_user_net* net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who) {
+    UserUnit* unit = nullptr;
+    if (int rc = matrix_core_unit(s, net->soft, net->activation, who, &unit)) return rc;
+    return with_mc_dims(s, who, [&](auto Nc, auto) -> int {
+        constexpr int N = decltype(Nc)::value;
+        UserBlobF blob = user_blob(s);
+        MlpP<N> p = make_mlp_params<N>(net->mean, net->std, net->xf, net->eps_scalar);
+        int64_t ngroups = 0, grid = 0;
+        if (int rc = mlp_value_grad_grid(B, 1, &ngroups, &grid, who)) return rc;
+        MlpHeadSoft soft = user_head(net);
+        MlpHeadPd pd{};
+        void* a[] = {&blob, &p, (void*)&net->W1, (void*)&net->W2, (void*)&net->W3, (void*)&x, (void*)&V, (void*)&g, (void*)&B, &ngroups,
+                     net->soft ? (void*)&soft : (void*)&pd};
+        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[0].c_str(), (unsigned)grid, kMcBlock, a, stream, who);
+    });
+}
+
+int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_user_net* net, int integrator, int t_first, int n_steps, int T_max,
+                      const float* x, float* traj, float* u_log, float* cost, float* done, float* resid, int32_t* done_step, float* x_out,
+                      const int32_t* order, int64_t B, void* workspace, void* stream, const char* who) {
+    if (integrator != HJBX_EULER && integrator != HJBX_RK4) return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: a user system steps with HJBX_EULER or HJBX_RK4", who);
+    UserUnit* unit = nullptr;
+    if (int rc = matrix_core_unit(s, net->soft, net->activation, who, &unit)) return rc;
+    return with_mc_dims(s, who, [&](auto Nc, auto Mc) -> int {
+        constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value;
+        UserBlobF blob = user_blob(s);
+        MlpP<N> p = make_mlp_params<N>(net->mean, net->std, net->xf, net->eps_scalar);
+        auto tk = make_task<float, N, M>(task);
+        auto lim = make_limits<float, M>(s);
+        RolloutOut<N, M> o{traj, u_log, cost, done, resid, done_step, x_out};
+        int64_t ngroups = 0, grid = 0;
+        int sched = 0;
+        if (int rc = mlp_rollout_grid(B, &ngroups, &grid, &sched, who)) return rc;
+        unsigned* ws = (unsigned*)workspace;
+        MlpHeadSoft soft = user_head(net);
+        MlpHeadPd pd{};
+        void* a[] = {&blob, &p, &tk, &lim, (void*)&net->W1, (void*)&net->W2, (void*)&net->W3, &t_first, &n_steps, &T_max, (void*)&x, (void*)&order,
+                     &o, (void*)&B, &ngroups, &ws, &sched, net->soft ? (void*)&soft : (void*)&pd};
+        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
+                           stream, who);
+    });
 }

@@ -168,5 +168,7 @@ using namespace hjbx;
                                                   x_final, B);                                                                             \
     }
 
+#ifndef HJBX_USER_MATRIX_CORE_UNIT   // the matrix-core unit (hjbx_user_mlp_kernels.hpp) takes UserSystem only: the streaming kernels exist already
 HJBX_U_KERNELS(float, f32)
 HJBX_U_KERNELS(double, f64)
+#endif

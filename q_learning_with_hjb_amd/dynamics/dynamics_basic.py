@@ -89,6 +89,8 @@ class Dynamics:
                 kind = {"affine": _abi.USER_AFFINE, "manipulator": _abi.USER_MANIPULATOR}[src["kind"]]
                 self._sys = _abi.SystemHandle.from_source(kind, src["source"], self.state_dim, self.control_dim, self.dt, self.umin, self.umax,
                                                           np.asarray(src.get("params", ()), np.float64))
+                if src.get("matrix_cores"):
+                    self._sys.enable_matrix_cores()      # NotImplementedError with the library's reason (e.g. an odd state dimension)
 
     # -- subclass hooks ---------------------------------------------------------------------------
     def _system_params(self, config) -> np.ndarray:
@@ -99,6 +101,8 @@ class Dynamics:
         library's streaming kernels compiled for this system at run time (hjbx_system_create_from_source; contract of the snippet:
         csrc/hjbx_user_kernels.hpp).  kind "manipulator": the snippet defines wrap, get_M, get_C, get_G, get_B and the generic
         manipulator form of dynamics_basic.py:64-94 is supplied; kind "affine": it defines wrap and affine (f1, f2) itself.
+        With matrix_cores=True in the dict the system also gets the two persistent matrix-core kernels of the value network (fused value
+        gradient and fused rollout under VHJBController), compiled at their first use; the state dimension must be even.
         Default: None -- such a subclass has no kernels and its compute methods raise NotImplementedError."""
         return None
 
