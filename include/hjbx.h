@@ -35,6 +35,7 @@ extern "C" {
 #define HJBX_VERSION 112 /* major*100 + minor */
 #define HJBX_HAS_REPLAY_APPEND 1 /* hjbx_replay_append_f32 / _f64 exist (added without a version step: an addition, nothing else changed) */
 #define HJBX_HAS_USER_MATRIX_CORES 1 /* hjbx_system_enable_matrix_cores / hjbx_system_matrix_cores / hjbx_system_code_object exist (an addition) */
+#define HJBX_HAS_USER_TRAIN 1 /* hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 take an enabled user-defined system; HJBX_CODE_TRAIN exists (an addition) */
 #define HJBX_MAX_N 10    /* largest state dimension (NearHoverQuadcopter) */
 #define HJBX_MAX_M 3     /* largest control dimension */
 
@@ -232,8 +233,7 @@ void hjbx_system_destroy(hjbx_system* sys);
  * hjbx_*_f32 / _f64 entry point of the HJBX_DECLARE block below (wrap, affine, dynamics_step, simulate with HJBX_EULER / HJBX_RK4,
  * initial_state, costs, control_from_grad, hjb_residual, vhjb_step, controller and rollout_feedback with HJBX_CTRL_LINEAR_FEEDBACK).
  * The matrix-core entry points (hjbx_value_grad_f32, hjbx_vhjb_rollout_f32, the two hjbx_softpd_* ones, hjbx_value_loss_grad_f32) return
- * HJBX_EUNSUPPORTED for such a handle unless it asked for them (hjbx_system_enable_matrix_cores below; the parameter gradient stays with
- * the built-in systems).  Compilation needs no GPU.  HJBX_EINVAL when the source does not compile
+ * HJBX_EUNSUPPORTED for such a handle unless it asked for them (hjbx_system_enable_matrix_cores below).  Compilation needs no GPU.  HJBX_EINVAL when the source does not compile
  * (hjbx_last_compile_log returns the compiler's messages for the calling thread's last call), HJBX_EUNSUPPORTED when libhiprtc.so
  * is not available. */
 int hjbx_system_create_from_source(int user_kind, const char* device_source, int n, int m, double dt, const double* umin,
@@ -248,17 +248,20 @@ size_t hjbx_last_compile_log(char* buf, size_t buflen);
  * csrc/hjbx_user_mlp_kernels.hpp (hiprtc, seconds, once per handle; a source that does not compile there: HJBX_EINVAL +
  * hjbx_last_compile_log; kernels that would spill registers to scratch: HJBX_EUNSUPPORTED; either way the handle keeps working with the
  * streaming entry points and the refusal is remembered).  float32 MFMA arithmetic only: with HJBX_OPT_MLP_ARITHMETIC != 0 the PD entry
- * points return HJBX_EUNSUPPORTED for such a handle.  Call it before the handle is shared between threads.
+ * points return HJBX_EUNSUPPORTED for such a handle.  The same call opens hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 to the handle
+ * (a third unit, compiled at their first call: see there).  Call it before the handle is shared between threads.
  * HJBX_EUNSUPPORTED when n is odd (the kernels walk the state in k-steps of 2); HJBX_EINVAL for a built-in handle. */
 int hjbx_system_enable_matrix_cores(hjbx_system* sys);
 /* 1 when the handle is a user-defined system with the matrix-core kernels enabled, 0 otherwise (built-in systems included). */
 int hjbx_system_matrix_cores(const hjbx_system* sys);
 /* The gfx950 code objects (ELF) a user-defined system runs (dynamics_basic.py:64-94 compiled; vhjb.py:17-60, 162-193, 201-202 for the
  * matrix-core units), for inspection: copies up to `len` bytes into buf (may be NULL) and returns the object's size.  `which` =
- * HJBX_CODE_STREAMING, or HJBX_CODE_MATRIX_CORES(head, activation) with head 0 = hjbx_mlp, 1 = hjbx_softpd_mlp -- compiled now if it has not
+ * HJBX_CODE_STREAMING, HJBX_CODE_MATRIX_CORES(head, activation) with head 0 = hjbx_mlp, 1 = hjbx_softpd_mlp, or HJBX_CODE_TRAIN(activation):
+ * the parameter-gradient unit of hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 (four kernels) -- compiled now if it has not
  * been yet.  Returns 0 on failure (hjbx_last_error; hjbx_last_compile_log when the compiler refused the source). */
 #define HJBX_CODE_STREAMING 0
 #define HJBX_CODE_MATRIX_CORES(head, activation) (1 + 3 * (head) + (activation))
+#define HJBX_CODE_TRAIN(activation) (7 + (activation))
 size_t hjbx_system_code_object(const hjbx_system* sys, int which, void* buf, size_t len);
 /* Dynamics.get_dimension, dynamics_basic.py:31-36 */
 int hjbx_dims(const hjbx_system* sys, int* n, int* m);
@@ -390,7 +393,15 @@ int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const
  * reverse sweep; both are evaluated in closed form (no autograd graph).  `mode` = hjbx_residual_mode.  Deterministic: no float atomics,
  * fixed summation order (the order depends on B and the device's CU count only).  ReLU, tanh and (state dimension <= 4) sin networks with features [128,128,64]
  * (HJBX_EUNSUPPORTED otherwise: the PyTorch autograd path remains); W1, W2, W3 16-byte aligned.  workspace: hjbx_value_loss_grad_workspace_bytes(B) bytes (it depends on
- * HJBX_OPT_MLP_ARITHMETIC / HJBX_OPT_TRAIN_KERNEL: ask again after changing them), 256-byte aligned, need not be initialised. */
+ * HJBX_OPT_MLP_ARITHMETIC / HJBX_OPT_TRAIN_KERNEL: ask again after changing them), 256-byte aligned, need not be initialised.
+ * User-defined systems (hjbx_system_create_from_source) after hjbx_system_enable_matrix_cores: the same arguments, workspace and results.
+ * All argument checks run first; then the first call for an activation compiles the cooperative kernel for the user's struct (hiprtc, seconds,
+ * at most once per handle; csrc/hjbx_user_train_kernels.hpp: residual mode 0 / 1 x large batch / minibatch = four kernels, PD network only).
+ * HJBX_EUNSUPPORTED -- nothing launched, the handle's streaming and rollout kernels keep working, the PyTorch autograd path remains -- when
+ * the handle has not been enabled, n is odd, the network is sin and n > 4, HJBX_OPT_MLP_ARITHMETIC != 0 or HJBX_OPT_TRAIN_KERNEL != 0 (float32
+ * MFMA arithmetic, cooperative kernel only; the message names the option), or when ANY of the four kernels needs scratch: the whole unit is
+ * refused, the message names the kernel and its bytes, and the refusal is remembered (a second call returns it at once).  HJBX_EINVAL +
+ * hjbx_last_compile_log when the source does not compile there. */
 size_t hjbx_value_loss_grad_workspace_bytes(int64_t B);
 int hjbx_value_loss_grad_f32(const hjbx_system* sys, const hjbx_task* task, const hjbx_mlp* mlp, int mode, const float* x,
                              const float* cost, const float* done, float* flat, void* workspace, int64_t B, void* stream);
@@ -425,7 +436,11 @@ int hjbx_mix_adam_f32(const float* flat, const float* reg_dev, double reg, doubl
  * buffer never materialised on the default (cooperative) path -- the reduction of the per-workgroup partial sums, the division by the counts,
  * the mix, the losses and Adam's update run in one epilogue kernel, i.e. two launches per update.  Arguments as in those two entry points;
  * adam->param[] must be the network's W1, W2, W3.  workspace: hjbx_value_loss_adam_workspace_bytes(B) bytes, 256-byte aligned, need not be
- * initialised.  (A data-parallel step needs the flat buffer for its all-reduce: hjbx_value_loss_grad_f32, all-reduce, hjbx_mix_adam_f32.) */
+ * initialised.  (A data-parallel step needs the flat buffer for its all-reduce: hjbx_value_loss_grad_f32, all-reduce, hjbx_mix_adam_f32.)
+ * The Adam state's shapes are checked before anything is launched: an HJBX_EINVAL leaves no kernel behind.
+ * User-defined systems after hjbx_system_enable_matrix_cores: as for hjbx_value_loss_grad_f32 -- the same run-time compiled unit, the same
+ * refusals (not enabled, odd n, sin with n > 4, HJBX_OPT_MLP_ARITHMETIC != 0, HJBX_OPT_TRAIN_KERNEL != 0, a kernel that needs scratch), all of
+ * them before the first launch -- followed by the library's own epilogue kernel. */
 size_t hjbx_value_loss_adam_workspace_bytes(int64_t B);
 /* optional last duty of that call: assemble the NEXT update's minibatch (what hjbx_replay_gather_f32 would do for index step_counter + 1, same
  * arguments and bounds behaviour) inside the epilogue kernel, so that a captured fit-phase update is two launches.  reg_out may be the buffer

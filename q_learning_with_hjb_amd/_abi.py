@@ -29,6 +29,7 @@ ROLLOUT_STOP_AT_TARGET = 2
 OPT_ROLLOUT_SCHEDULE, OPT_ROLLOUT_EXTRA_WORKGROUPS, OPT_STREAM_ROWS, OPT_MLP_ARITHMETIC, OPT_TRAIN_KERNEL = 0, 1, 2, 3, 4
 OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE = 0, -1, -2, -3, -4
 CODE_STREAMING = 0
+CODE_TRAIN = 7          # HJBX_CODE_TRAIN(activation) = 7 + activation: the parameter-gradient unit of a user-defined system
 _HEADS = {"pd": 0, "soft": 1}
 _ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sin": ACT_SIN}
 
@@ -51,7 +52,7 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds the device headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
 _HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
-            "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", os.path.join("..", "..", "include", "hjbx.h"))
+            "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
 class HjbxAdamState(C.Structure):
@@ -403,6 +404,7 @@ class SystemHandle:
         self.umax = np.ascontiguousarray(umax, np.float64).reshape(m)
         self.params = np.ascontiguousarray(params, np.float64).ravel()
         self.user_kind, self.device_source = int(user_kind), str(device_source)
+        self.param_grad = False      # Dynamics.device_source(param_grad=True): controllers fuse the parameter gradient by default
         h = _VP()
         rc = lib().hjbx_system_create_from_source(self.user_kind, self.device_source.encode(), self.n, self.m, self.dt, self.umin.ctypes.data,
                                                   self.umax.ctypes.data, self.params.ctypes.data if self.params.size else None,
@@ -426,14 +428,15 @@ class SystemHandle:
 
     def code_object(self, which="streaming") -> bytes:
         """hjbx_system_code_object: the gfx950 ELF this user-defined system runs.  which = "streaming" (compiled at creation) or
-        (head, activation) with head in ("pd", "soft") and activation in ("relu", "tanh", "sin"): the matrix-core unit, compiled now if
-        it has not been.  NotImplementedError when the handle has not enabled the matrix-core kernels or the library refuses to ship the
+        (head, activation) with head in ("pd", "soft") and activation in ("relu", "tanh", "sin"): the matrix-core unit, or
+        ("train", activation): the parameter-gradient unit (the four k_train_coop kernels of hjbx_value_loss_grad_f32 /
+        hjbx_value_loss_adam_f32) -- compiled now if it has not been.  NotImplementedError when the handle has not enabled the matrix-core kernels or the library refuses to ship the
         unit, ValueError (with the compiler's log) when the source does not compile there."""
         if which == "streaming":
             code = CODE_STREAMING
         else:
             head, act = which
-            code = 1 + 3 * _HEADS[head] + _ACTIVATIONS[act]
+            code = CODE_TRAIN + _ACTIVATIONS[act] if head == "train" else 1 + 3 * _HEADS[head] + _ACTIVATIONS[act]
         size = lib().hjbx_system_code_object(self._h, code, None, 0)
         if size == 0:
             msg = last_error()

@@ -13,6 +13,7 @@ in lock-step, state resident in HBM, time-major logs `(T+1, B, ...)`.
 from __future__ import annotations
 
 import math
+import warnings
 import weakref
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -378,6 +379,47 @@ class ReplayBuffer:
 
 class VHJBController(Controller):
 
+    @staticmethod
+    def _choose_fused_param_grad(dynamics, config, dtype, activation, soft, device, fused_param_grad) -> bool:
+        """Whether params_update takes the fused parameter-gradient kernels.  fused_param_grad: None = automatic, True = demanded
+        (NotImplementedError when impossible), False = autograd."""
+        builtin = dynamics.system.kind != _abi.SYS_USER
+        # the parameter gradient of the optimiser step: hand-written MFMA kernels (hjbx_value_loss_grad_f32: forward, input gradient,
+        # residuals and the second-order reverse sweep in closed form) for the float32 ReLU network of controller/vhjb.py, the tanh network
+        # of examples/cartpole_balancing.ipynb and (state dimension <= 4) the sin network of examples/double_integrator_optimal_time.ipynb;
+        # anything else (float64, HJBX_FUSED_PARAM_GRAD=0) goes through PyTorch autograd.  A user-defined system with the matrix-core
+        # kernels enabled gets the same kernel compiled for its own struct when it asks for it -- param_grad=True in device_source() for the
+        # automatic mode, or fused_param_grad=True here; without either such a system keeps autograd, as before.  The handle is asked for
+        # that unit HERE (seconds, once per handle and activation), because the library refuses the whole unit when one of its kernels
+        # would need scratch -- then the controller trains through autograd, after one warning in automatic mode and with
+        # NotImplementedError when fusion was demanded
+        net_ok = (not soft and dtype == torch.float32 and (activation in ("relu", "tanh") or (activation == "sin" and dynamics.get_dimension()[0] <= 4))
+                  and tuple(config.features) == (128, 128, 64) and not config.using_batch_norm)
+        if fused_param_grad is None and os.environ.get("HJBX_FUSED_PARAM_GRAD", "1") == "0":
+            fused_param_grad = False
+        user_refusal = None
+        if not builtin and fused_param_grad is None and not getattr(dynamics.system, "param_grad", False):
+            fused_param_grad = False
+        if not builtin and net_ok and device.type == "cuda" and dynamics.system.matrix_cores and fused_param_grad is not False:
+            try:
+                dynamics.system.code_object(("train", activation))
+            except (NotImplementedError, ValueError) as err:
+                user_refusal = str(err)
+        can_fuse_pg = net_ok and device.type == "cuda" and (builtin or (dynamics.system.matrix_cores and user_refusal is None))
+        if fused_param_grad is None:
+            if user_refusal is not None:
+                warnings.warn(f"no fused parameter gradient for this user-defined system, training through autograd: {user_refusal}", RuntimeWarning,
+                              stacklevel=3)
+            fused_param_grad = can_fuse_pg
+        if fused_param_grad and soft:
+            raise NotImplementedError("there is no fused parameter-gradient kernel for the soft-PD value network (it trains through autograd)")
+        if fused_param_grad and user_refusal is not None:
+            raise NotImplementedError(user_refusal)
+        if fused_param_grad and not can_fuse_pg:
+            raise NotImplementedError("the fused parameter-gradient kernels exist for float32 ReLU / tanh / sin (n <= 4) networks with features "
+                                      "[128, 128, 64] on the built-in systems and on user-defined systems with matrix_cores=True")
+        return bool(fused_param_grad)
+
     def __init__(self, dynamics: Dynamics, config, device=None, dtype=torch.float32, process_group=None,
                  residual_mode=_abi.RESIDUAL_NORMALISED, fused_value_grad: Optional[bool] = None,
                  graph_updates: Optional[bool] = None, activation: str = "relu", fused_param_grad: Optional[bool] = None,
@@ -437,26 +479,13 @@ class VHJBController(Controller):
         # activation: "relu" = controller/vhjb.py; "tanh" / "sin" = the notebooks' networks
         # the matrix-core kernels carry the five built-in systems, and a user-defined system (Dynamics.device_source) that asked for
         # them (matrix_cores=True: value gradient and fused rollout compiled at first use); any other user system runs the value network
-        # through PyTorch and its own run-time compiled step / residual kernels.  The parameter gradient of a user system always does.
+        # through PyTorch and its own run-time compiled step / residual kernels.
         builtin = dynamics.system.kind != _abi.SYS_USER
         fusable = activation in ValueFunctionApproximator.FUSED_ACTIVATIONS and (builtin or dynamics.system.matrix_cores)
         self.fused_value_grad = (dtype == torch.float32 and fusable) if fused_value_grad is None else bool(fused_value_grad)
         if self.fused_value_grad and not fusable:
             raise NotImplementedError(f"no fused value-gradient kernel for the {activation} activation")
-        # the parameter gradient of the optimiser step: hand-written MFMA kernels (hjbx_value_loss_grad_f32: forward, input gradient,
-        # residuals and the second-order reverse sweep in closed form) for the float32 ReLU network of controller/vhjb.py, the tanh network
-        # of examples/cartpole_balancing.ipynb and (state dimension <= 4) the sin network of examples/double_integrator_optimal_time.ipynb;
-        # anything else (float64, HJBX_FUSED_PARAM_GRAD=0) goes through PyTorch autograd
-        can_fuse_pg = (not soft and dtype == torch.float32 and (activation in ("relu", "tanh") or (activation == "sin" and self.state_dim <= 4))
-                       and tuple(config.features) == (128, 128, 64) and self.device.type == "cuda" and not config.using_batch_norm and builtin)
-        if fused_param_grad is None:
-            fused_param_grad = can_fuse_pg and os.environ.get("HJBX_FUSED_PARAM_GRAD", "1") != "0"
-        if fused_param_grad and soft:
-            raise NotImplementedError("there is no fused parameter-gradient kernel for the soft-PD value network (it trains through autograd)")
-        if fused_param_grad and not can_fuse_pg:
-            raise NotImplementedError("the fused parameter-gradient kernels exist for float32 ReLU / tanh / sin (n <= 4) networks with features "
-                                      "[128, 128, 64] on the built-in systems only")
-        self.fused_param_grad = bool(fused_param_grad)
+        self.fused_param_grad = self._choose_fused_param_grad(dynamics, config, dtype, activation, soft, self.device, fused_param_grad)
         # fused rollouts of big batches re-pack live environments every `compaction_interval` steps (0 = never)
         self.compaction_interval, self.compaction_min_batch = 16, 8192
         self.train_mode = False

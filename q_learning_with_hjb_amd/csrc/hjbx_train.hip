@@ -654,6 +654,22 @@ static int check_vlg(const char* who, const hjbx_system* sys, const hjbx_task* t
     return HJBX_OK;
 }
 
+// A user-defined system (hjbx_system_create_from_source) takes the cooperative kernel only, compiled for it at run time (hjbx_user.hip):
+// float32 MFMA arithmetic, no round-2 pair.  HJBX_OK when the call may go on to hjbx_train_coop.
+static int check_user_train(const char* who, const hjbx_system* sys) {
+    if (sys->n % 2)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the fused parameter gradient needs an even state dimension (k-steps of 2), got n=%d", who, sys->n);
+    if (!hjbx_user_matrix_cores(sys))
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
+    if (hjbx_option_value(HJBX_OPT_MLP_ARITHMETIC) != 0)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: HJBX_OPT_MLP_ARITHMETIC=%d (split-operand MFMA) is not compiled for user-defined systems; set it to 0", who,
+                              hjbx_option_value(HJBX_OPT_MLP_ARITHMETIC));
+    if (hjbx_option_value(HJBX_OPT_TRAIN_KERNEL) != 0)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: HJBX_OPT_TRAIN_KERNEL=%d (the round-2 pair of kernels) is not compiled for user-defined systems; set it to 0", who,
+                              hjbx_option_value(HJBX_OPT_TRAIN_KERNEL));
+    return HJBX_OK;
+}
+
 // the round-2 pair of kernels -> flat (arguments already validated)
 static int run_pair(const hjbx_system* sys, const hjbx_task* task, const hjbx_mlp* mlp, int mode, const float* x, const float* cost, const float* done,
                     float* flat, void* workspace, int64_t B, void* stream) {
@@ -682,6 +698,10 @@ extern "C" int hjbx_value_loss_grad_f32(const hjbx_system* sys, const hjbx_task*
         hipError_t e = hipMemsetAsync(flat, 0, (2 * P + 4) * sizeof(float), (hipStream_t)stream);
         if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
         return HJBX_OK;
+    }
+    if (sys->kind == HJBX_SYS_USER) {
+        if (int rc = check_user_train("hjbx_value_loss_grad_f32", sys)) return rc;
+        return hjbx_train_coop(sys, task, mlp, mode, x, cost, done, flat, workspace, B, stream, nullptr);
     }
     if (!use_two_kernels(mlp->activation)) return hjbx_train_coop(sys, task, mlp, mode, x, cost, done, flat, workspace, B, stream, nullptr);
     return run_pair(sys, task, mlp, mode, x, cost, done, flat, workspace, B, stream);
@@ -724,6 +744,10 @@ extern "C" int hjbx_value_loss_adam_f32(const hjbx_system* sys, const hjbx_task*
             return hjbx_set_error(HJBX_EINVAL, "hjbx_value_loss_adam_f32: next minibatch: bad n, batch, capacity, lengths, or reg_out without reg_table");
         f.next = GatherArgs{next->buf_x, next->buf_cost, next->buf_done, next->capacity, next->n, next->perm, next->perm_len, next->reg_table, next->table_len,
                             next->batch, next->xs, next->costs, next->dones, next->reg_out, 1};
+    }
+    if (sys->kind == HJBX_SYS_USER) {
+        if (int rc = check_user_train("hjbx_value_loss_adam_f32", sys)) return rc;
+        return hjbx_train_coop(sys, task, mlp, mode, x, cost, done, nullptr, workspace, B, stream, &f);
     }
     if (!use_two_kernels(mlp->activation)) return hjbx_train_coop(sys, task, mlp, mode, x, cost, done, nullptr, workspace, B, stream, &f);
     float* flat = reinterpret_cast<float*>(static_cast<char*>(workspace) + ((hjbx_value_loss_grad_workspace_bytes(B) + 255) & ~(size_t)255));

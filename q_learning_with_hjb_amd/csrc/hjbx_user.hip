@@ -7,7 +7,9 @@
 // (controller/vhjb.py:17-60, 162-193, 201-202: network, its input gradient, the closed loop): a second translation unit,
 // hjbx_user_mlp_kernels.hpp, compiled at the first call for each (head, activation) and kept in the handle; hjbx_mlp.hip and
 // hjbx_softpd.hip hand an enabled user handle over to hjbx_user_value_grad / hjbx_user_rollout below.  The parameter gradient
-// (hjbx_value_loss_grad_f32) stays with the built-in systems.
+// (hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32) is a third unit, hjbx_user_train_kernels.hpp: the cooperative kernel k_train_coop
+// for the user's struct, one unit per activation (PD head only), compiled at its first use and refused as a whole when one of its four
+// kernels needs scratch; hjbx_train_coop.hip builds the arguments and launches it through hjbx_user_train_launch below.
 //
 // hiprtc is opened with dlopen at first use: libhjbx.so has no link-time dependency on it, and a process that never creates a user system
 // never loads it.  Compilation needs no GPU (the CPU test compiles a snippet); modules are loaded per device at the first launch.
@@ -46,6 +48,8 @@ HJBX_EMBED(hjbx_src_mlp_core, "hjbx_mlp_core.hpp");
 HJBX_EMBED(hjbx_src_mlp_kernels, "hjbx_mlp_kernels.hpp");
 HJBX_EMBED(hjbx_src_mlp_x3, "hjbx_mlp_x3.hpp");
 HJBX_EMBED(hjbx_src_mlp_h2, "hjbx_mlp_h2.hpp");
+HJBX_EMBED(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp");
+HJBX_EMBED(hjbx_src_user_train, "hjbx_user_train_kernels.hpp");
 HJBX_EMBED(hjbx_src_abi, "../../include/hjbx.h");
 #endif
 extern "C" const char hjbx_src_systems[];
@@ -56,6 +60,8 @@ extern "C" const char hjbx_src_mlp_core[];
 extern "C" const char hjbx_src_mlp_kernels[];
 extern "C" const char hjbx_src_mlp_x3[];
 extern "C" const char hjbx_src_mlp_h2[];
+extern "C" const char hjbx_src_train_coop[];
+extern "C" const char hjbx_src_user_train[];
 extern "C" const char hjbx_src_abi[];
 
 // what hiprtc's built-in runtime header does not bring: the system headers the library's own headers include, as far as they use them
@@ -125,7 +131,7 @@ struct UserUnit {
     // second call reports them again instead of compiling for another 20 s)
     int state = 0, status = HJBX_OK;
     std::string error, log;
-    std::string kernel[3];                           // symbols of: value gradient, Euler rollout, RK4 rollout
+    std::string kernel[4];                           // symbols of: value gradient, Euler rollout, RK4 rollout (a train unit: kTrainKernels)
 };
 
 struct UserProgram {
@@ -137,17 +143,23 @@ struct UserProgram {
     std::mutex mc_mu;                                // guards `matrix_cores` and the state of mc[][] (held across a lazy compile)
     bool matrix_cores = false;                       // hjbx_system_enable_matrix_cores
     UserUnit mc[2][3];                               // [head: 0 PD, 1 soft-PD][hjbx_activation]
+    std::mutex train_mu;                             // guards the state of train[] (held across a lazy compile)
+    UserUnit train[3];                               // [hjbx_activation]: the parameter-gradient unit (hjbx_user_train_kernels.hpp), PD head
 };
+
+// the four kernels of a train unit, in the order of UserUnit::kernel: index = 2 * residual mode + (PS == 4)
+const char* const kTrainKernels[4] = {"HJBX_UT_M0_PS1", "HJBX_UT_M0_PS4", "HJBX_UT_M1_PS1", "HJBX_UT_M1_PS4"};
+const char* const kTrainLabels[4] = {"k_train_coop<mode 0, PS 1>", "k_train_coop<mode 0, PS 4>", "k_train_coop<mode 1, PS 1>", "k_train_coop<mode 1, PS 4>"};
 
 // Compile `top` (one #include line) for the user's snippet with the library's own flags + `extra`; name expressions are resolved into
 // out->kernel[].  Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
 int compile_unit(const Rtc& R, const char* who, const char* top, const char* unit_name, const std::string& snippet, int user_kind, int n, int m,
                  int np, const std::vector<std::string>& extra, const std::vector<const char*>& name_exprs, UserUnit* out) {
     const char* headers[] = {hjbx_src_systems, hjbx_src_stream, hjbx_src_user, hjbx_src_user_mlp, hjbx_src_mlp_core, hjbx_src_mlp_kernels,
-                             hjbx_src_mlp_x3, hjbx_src_mlp_h2, hjbx_src_abi, kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint,
+                             hjbx_src_mlp_x3, hjbx_src_mlp_h2, hjbx_src_train_coop, hjbx_src_user_train, hjbx_src_abi, kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint,
                              kStubStddef, kStubStddef, kStubTypeTraits};
     const char* names[] = {"hjbx_systems.hpp", "hjbx_stream_kernels.hpp", "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_core.hpp",
-                           "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx.h", "hjbx_internal.hpp", "hjbx_user_snippet.hpp",
+                           "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx.h", "hjbx_internal.hpp", "hjbx_user_snippet.hpp",
                            "hip/hip_runtime.h", "stdint.h", "stddef.h", "cstddef", "type_traits"};
     static_assert(sizeof(headers) == sizeof(names), "one name per header");
     hiprtcProgram prog = nullptr;
@@ -177,7 +189,7 @@ int compile_unit(const Rtc& R, const char* who, const char* top, const char* uni
     if (R.code_size(prog, &cs) != HIPRTC_SUCCESS || cs == 0) { R.destroy(&prog); return hjbx_set_error(HJBX_EHIP, "%s: no code object", who); }
     out->code.resize(cs);
     hiprtcResult rg = R.code(prog, out->code.data());
-    for (size_t i = 0; rg == HIPRTC_SUCCESS && i < name_exprs.size() && i < 3; ++i) {
+    for (size_t i = 0; rg == HIPRTC_SUCCESS && i < name_exprs.size() && i < 4; ++i) {
         const char* low = nullptr;
         rg = R.lowered(prog, name_exprs[i], &low);
         if (rg == HIPRTC_SUCCESS && low) out->kernel[i] = low;
@@ -290,6 +302,55 @@ int matrix_core_unit(const hjbx_system* s, int soft, int act, const char* who, U
     *out = &unit;
     return HJBX_OK;
 }
+
+// The train unit of an enabled handle for `act`, compiled now if this is the first call that needs it.  One wave per SIMD and 512 registers:
+// when ANY of the four kernels needs scratch the whole unit is refused (a controller trains fused or it does not), the code object is
+// dropped and the refusal remembered; the handle keeps its streaming and rollout units.
+int train_unit(const hjbx_system* s, int act, const char* who, UserUnit** out) {
+    UserProgram* u = s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "%s: not a user-defined system", who);
+    if (act < 0 || act > 2) return hjbx_set_error(HJBX_EINVAL, "%s: unknown activation %d", who, act);
+    if (s->n % 2)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the fused parameter gradient needs an even state dimension (k-steps of 2), got n=%d", who, s->n);
+    if (!hjbx_user_matrix_cores(s))
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
+    if (act == HJBX_ACT_SIN && s->n > 4)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the sin network's fused parameter gradient exists for n <= 4 (n = %d)", who, s->n);
+    std::lock_guard<std::mutex> lock(u->train_mu);
+    UserUnit& unit = u->train[act];
+    if (unit.state == 0) {
+        g_compile_log.clear();
+        const Rtc& R = rtc();   // (loaded: the handle was created through it)
+        // (the library's common flags only: with -fno-slp-vectorize, which hjbx_train_coop.hip's own build adds, hiprtc's compiler needs
+        //  16-72 bytes of scratch for the tanh / sin kernels of the test systems)
+        int rc = compile_unit(R, who, "#include \"hjbx_user_train_kernels.hpp\"\n", "hjbx_user_train.hip", u->source, u->user_kind, u->n, u->m, u->np,
+                              {"-DHJBX_USER_MLP_ACT=" + std::to_string(act)},
+                              {kTrainKernels[0], kTrainKernels[1], kTrainKernels[2], kTrainKernels[3]}, &unit);
+        for (int k = 0; rc == HJBX_OK && k < 4; ++k) {
+            const long scratch = kernel_scratch_bytes(unit.code, unit.kernel[k]);
+            if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, unit.kernel[k].c_str());
+            else if (scratch > 0)
+                rc = hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the %s kernel of this user system (n=%d m=%d, activation %d) needs %ld bytes of scratch: its "
+                                    "code does not fit the 512 registers of the cooperative parameter-gradient kernel; the fused parameter gradient "
+                                    "is refused for this system", who, kTrainLabels[k], u->n, u->m, act, scratch);
+        }
+        unit.state = rc == HJBX_OK ? 1 : -1;
+        unit.status = rc;
+        unit.log = g_compile_log;
+        if (rc != HJBX_OK) {
+            char msg[512];
+            hjbx_last_error(msg, sizeof msg);
+            unit.error = msg;
+            unit.code.clear();
+        }
+    }
+    if (unit.state < 0) {
+        g_compile_log = unit.log;
+        return hjbx_set_error(unit.status, "%s", unit.error.c_str());
+    }
+    *out = &unit;
+    return HJBX_OK;
+}
 }  // namespace
 
 extern "C" size_t hjbx_last_compile_log(char* buf, size_t buflen) {
@@ -308,6 +369,7 @@ void hjbx_user_release(void* up) {
     unload_unit(u->stream);
     for (auto& head : u->mc)
         for (UserUnit& unit : head) unload_unit(unit);
+    for (UserUnit& unit : u->train) unload_unit(unit);
     delete u;
 }
 
@@ -376,9 +438,13 @@ extern "C" size_t hjbx_system_code_object(const hjbx_system* sys, int which, voi
     if (!u) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: not a user-defined system"); return 0; }
     const UserUnit* unit = &u->stream;
     if (which != HJBX_CODE_STREAMING) {
-        if (which < 1 || which > 6) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: unknown code object %d", which); return 0; }
+        if (which < 1 || which > 9) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: unknown code object %d", which); return 0; }
         UserUnit* mc = nullptr;
-        if (matrix_core_unit(sys, (which - 1) / 3, (which - 1) % 3, "hjbx_system_code_object", &mc) != HJBX_OK) return 0;
+        if (which >= 7) {
+            if (train_unit(sys, which - 7, "hjbx_system_code_object", &mc) != HJBX_OK) return 0;
+        } else if (matrix_core_unit(sys, (which - 1) / 3, (which - 1) % 3, "hjbx_system_code_object", &mc) != HJBX_OK) {
+            return 0;
+        }
         unit = mc;
     }
     if (buf && len) memcpy(buf, unit->code.data(), len < unit->code.size() ? len : unit->code.size());
@@ -459,4 +525,19 @@ int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_us
         return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
                            stream, who);
     });
+}
+
+// ---- the parameter gradient of an enabled handle (called by hjbx_train_coop.hip) ----------------------------------------------------
+int hjbx_user_train_unit(const hjbx_system* s, int activation, const char* who) {
+    UserUnit* unit = nullptr;
+    return train_unit(s, activation, who, &unit);
+}
+
+int hjbx_user_train_launch(const hjbx_system* s, int activation, int mode, int psplit, unsigned grid, void** args, void* stream, const char* who) {
+    if (mode < 0 || mode > 1 || (psplit != 1 && psplit != 4)) return hjbx_set_error(HJBX_EINVAL, "%s: residual mode %d / psplit %d", who, mode, psplit);
+    UserUnit* unit = nullptr;
+    if (int rc = train_unit(s, activation, who, &unit)) return rc;
+    UserBlobF blob = user_blob(s);
+    args[0] = &blob;
+    return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[2 * mode + (psplit == 4 ? 1 : 0)].c_str(), grid, 256, args, stream, who);
 }

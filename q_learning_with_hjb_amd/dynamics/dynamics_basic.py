@@ -91,6 +91,10 @@ class Dynamics:
                                                           np.asarray(src.get("params", ()), np.float64))
                 if src.get("matrix_cores"):
                     self._sys.enable_matrix_cores()      # NotImplementedError with the library's reason (e.g. an odd state dimension)
+                    # param_grad=True: VHJBController also takes the fused parameter gradient for this system by default
+                    self._sys.param_grad = bool(src.get("param_grad"))
+                elif src.get("param_grad"):
+                    raise ValueError("device_source(): param_grad=True needs matrix_cores=True (the fused parameter gradient is a matrix-core kernel)")
 
     # -- subclass hooks ---------------------------------------------------------------------------
     def _system_params(self, config) -> np.ndarray:
@@ -103,6 +107,9 @@ class Dynamics:
         manipulator form of dynamics_basic.py:64-94 is supplied; kind "affine": it defines wrap and affine (f1, f2) itself.
         With matrix_cores=True in the dict the system also gets the two persistent matrix-core kernels of the value network (fused value
         gradient and fused rollout under VHJBController), compiled at their first use; the state dimension must be even.
+        With param_grad=True as well, VHJBController's learning step takes the fused parameter-gradient kernel compiled for this system
+        (float32 PD network; asked for when the controller is constructed) instead of autograd, unless the library refuses the unit:
+        then the controller warns once and keeps autograd.  Without it, VHJBController(..., fused_param_grad=True) asks for the same.
         Default: None -- such a subclass has no kernels and its compute methods raise NotImplementedError."""
         return None
 
