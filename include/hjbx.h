@@ -492,6 +492,38 @@ int hjbx_replay_append_f32(const float* traj, const float* cost, const int32_t* 
 int hjbx_replay_append_f64(const double* traj, const double* cost, const int32_t* done_step, int64_t T, int64_t B, int n, double* buf_x,
                            double* buf_cost, double* buf_done, int64_t capacity, int64_t head, int64_t* header, void* workspace, void* stream);
 
+/* Dynamics.get_initial_state (dynamics_basic.py:28-29) with the uniforms drawn on the device: x0[i] = wrap(-x0_std + 2 x0_std u(i) + x0_mean),
+ * the statement (and the code) of hjbx_initial_state_*, where the n uniforms of row r = first_row + i come from Philox4x32-10 (round
+ * multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) under key (lo32(seed), hi32(seed)) at counter
+ * (lo32(r), hi32(r), g, 0):
+ *   float32: component k takes word k % 4 of group g = k / 4,                      u = float(w >> 8) 2^-24;
+ *   float64: component k takes words a = 2 (k % 2), b = a + 1 of group g = k / 2,  u = ((w_a >> 5) 2^26 + (w_b >> 6)) 2^-53.
+ * A row depends on (seed, r) only: batch size, grid, the split of a batch into calls, rank and call order have no effect, so disjoint row
+ * ranges of one seed are disjoint parts of one stream.  No u01 buffer, no generator state in memory, no atomics.  Built-in systems run one
+ * fused kernel; for a HJBX_SYS_USER handle the library writes the same uniforms into a (B, n) temporary of its own (stream-ordered) and
+ * runs the handle's hjbx_initial_state_* kernel on it: the same bits.
+ * HJBX_EINVAL before anything is enqueued: a NULL handle, x0_mean, x0_std or x0, a misaligned x0, B < 0.  B == 0: HJBX_OK, nothing launched. */
+#define HJBX_HAS_DEVICE_COLLECTION 1 /* the four entry points below exist (an addition, nothing else changed) */
+int hjbx_initial_state_philox_f32(const hjbx_system* sys, const double* x0_mean, const double* x0_std, uint64_t seed, uint64_t first_row,
+                                  float* x0, int64_t B, void* stream);
+int hjbx_initial_state_philox_f64(const hjbx_system* sys, const double* x0_mean, const double* x0_std, uint64_t seed, uint64_t first_row,
+                                  double* x0, int64_t B, void* stream);
+
+/* The statistics of an epoch's rollouts (vhjb.py:302-307: the trajectories; :326-329: mean and np.var(...)**0.5 of their costs, mean length)
+ * from the contiguous time-major (S, B) cost log of hjbx_rollout_feedback_* / the fused rollouts.  Tuple t of environment b counts iff
+ * t <= done_step[b]; entries past it are never read (a NaN there is not seen), and a done_step outside [0, S-1] is held to that range
+ * (a negative one counts no tuple), so no content of done_step leads outside the log.
+ *   traj_cost (B,) or NULL: the float64 sum of cost[0..done_step[b], b] in time order (one sequential chain per environment).
+ *   stats[4] = { sum_b c_b, sum_b (c_b - mean)^2 with mean = stats[0] / B, sum_b (done_step[b] + 1), B }: summed over b in a fixed order
+ *              without float atomics, bit-identical from call to call.  Mean, population standard deviation and mean length follow on the host.
+ *   workspace: hjbx_reduce_workspace_bytes() bytes under that function's contract (zero-filled once, left zeroed, one stream at a time).
+ * Two launches, no host synchronisation.  HJBX_EINVAL before anything is enqueued: NULL cost, done_step, stats or workspace, a misaligned
+ * buffer, S < 1, B < 0.  B == 0: HJBX_OK, nothing launched, stats untouched. */
+int hjbx_rollout_cost_stats_f32(const float* cost, const int32_t* done_step, int64_t S, int64_t B, double* traj_cost, double* stats,
+                                void* workspace, void* stream);
+int hjbx_rollout_cost_stats_f64(const double* cost, const int32_t* done_step, int64_t S, int64_t B, double* traj_cost, double* stats,
+                                void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,44 @@ def initial_state(sys, x0_mean, x0_std, u01):
     return x0
 
 
+def initial_state_philox(sys, x0_mean, x0_std, batch_size, seed, first_row=0, dtype=torch.float32, out=None, device=None):
+    """hjbx_initial_state_philox_*: (B, n) start states whose uniforms the kernel draws itself -- row i from (seed, first_row + i) alone
+    (Philox4x32-10; the stream is defined in include/hjbx.h).  seed and first_row are unsigned 64-bit."""
+    import numpy as np
+    B, seed, first_row = int(batch_size), int(seed), int(first_row)
+    if B < 0:
+        raise ValueError(f"batch_size must be non-negative, got {B}")
+    if not 0 <= seed < 1 << 64 or not 0 <= first_row < 1 << 64:
+        raise ValueError("seed and first_row must fit an unsigned 64-bit integer")
+    if first_row + B > 1 << 64:
+        raise ValueError("first_row + batch_size runs past the end of the stream (2^64 rows)")
+    mean = np.ascontiguousarray(x0_mean, np.float64).reshape(sys.n)
+    std = np.ascontiguousarray(x0_std, np.float64).reshape(sys.n)
+    if out is None:
+        out = torch.empty((B, sys.n), dtype=dtype, device=require_device() if device is None else device)
+    _chk(out, "out", (B, sys.n), dtype)
+    check(_fn("initial_state_philox", out)(sys.ptr, mean.ctypes.data, std.ctypes.data, seed, first_row, _p(out), B, _stream()))
+    return out
+
+
+def rollout_cost_stats(cost, done_step, want_traj_cost=True):
+    """hjbx_rollout_cost_stats_*: cost (S, B) time-major log, done_step (B,) int32 -> (traj_cost (B,) float64 or None, stats (4,) float64
+    on the device = {sum c, sum (c - mean)^2, sum (done_step + 1), B}); tuples past done_step are never read."""
+    if cost.dim() != 2:
+        raise ValueError(f"cost must be the (S, B) log, got shape {tuple(cost.shape)}")
+    S, B = cost.shape
+    _sfx(cost)
+    _chk(cost, "cost", (S, B))
+    _chk(done_step, "done_step", (B,), torch.int32)
+    if S < 1:
+        raise ValueError("cost must hold at least one time step")
+    traj_cost = torch.empty((B,), dtype=torch.float64, device=cost.device) if want_traj_cost else None
+    stats = torch.zeros((4,), dtype=torch.float64, device=cost.device)
+    ws = _workspaces(cost.device).reduce()
+    check(_fn("rollout_cost_stats", cost)(_p(cost), _p(done_step), S, B, _p(traj_cost), _p(stats), _p(ws), _stream()))
+    return traj_cost, stats
+
+
 def running_cost(sys, task, x, u):
     B = x.shape[0]
     _chk(x, "x", (B, sys.n))

@@ -424,7 +424,7 @@ class VHJBController(Controller):
                  residual_mode=_abi.RESIDUAL_NORMALISED, fused_value_grad: Optional[bool] = None,
                  graph_updates: Optional[bool] = None, activation: str = "relu", fused_param_grad: Optional[bool] = None,
                  value_structure: str = "pd", soft_pd_regularization: float = 1.0, soft_pd_warmup_epochs: int = 0,
-                 device_replay_append: bool = True) -> None:
+                 device_replay_append: bool = True, device_collection: bool = False) -> None:
         super().__init__()
         # value_structure: "pd" = ValueFunctionApproximator (controller/vhjb.py); "soft_pd" = SoftPDValueFunctionApproximator, trained with
         # the hinge soft_pd_regularization * mean(relu(V(xf) - V(x))) on top of the HJB loss, after soft_pd_warmup_epochs epochs of fitting
@@ -448,6 +448,13 @@ class VHJBController(Controller):
         self._gen.manual_seed(config.seed + self.rank)
         self._init_gen = torch.Generator(device=self.device)
         self._init_gen.manual_seed(config.seed)  # identical initial weights on every rank
+        # device_collection=True: train() and warm_start() draw their start states with Dynamics.sample_initial_states (rows of the one stream
+        # of config.seed: rank r takes rows_drawn + r ntraj .. + ntraj, then every rank advances rows_drawn by ntraj world_size) and take the
+        # trajectory-cost statistics from hjbx_rollout_cost_stats_*: no NumPy draw, no copy of x0, no (T+1, B) temporary, one read-back of
+        # four doubles.  Off (the default): the reference's NumPy stream, draw for draw.
+        self.device_collection = bool(device_collection)
+        self.collection_seed = int(config.seed) % (1 << 64)
+        self.rows_drawn = 0
 
         self.epsilon = float(config.epsilon)
         self.dynamics = dynamics
@@ -669,11 +676,17 @@ class VHJBController(Controller):
         Returns dict(records, average_trajectory_cost, average_trajectory_length, done_step)."""
         T = self.maximum_timestep if max_steps is None else int(max_steps)
         if x0 is None:
-            x0 = self.dynamics.get_initial_state(batch_size=int(num_of_trajectories))
+            x0 = self._draw_start_states(int(num_of_trajectories)) if self.device_collection else \
+                self.dynamics.get_initial_state(batch_size=int(num_of_trajectories))
         x0 = self._dev(np.atleast_2d(x0) if isinstance(x0, np.ndarray) else x0).contiguous()
         B = x0.shape[0]
         out = _ops.rollout_feedback(self.dynamics.system, controller._descriptor(), x0, T, task=self._task,
                                     integrator=self.dynamics.integrator, terminate=True, log_traj=True, log_u=False, log_cost=True)
+        if self.device_collection:
+            records = self._append_rollout(out)
+            total, _, tuples, count = self._cost_stats(out)
+            return dict(records=records, average_trajectory_cost=total / count, average_trajectory_length=tuples / count,
+                        done_step=out["done_step"])
         ds = out["done_step"].long()
         steps = torch.arange(T + 1, device=self.device)[:, None]
         valid = steps <= ds[None, :]                                  # (T+1, B): tuples up to and including the terminal one
@@ -681,6 +694,18 @@ class VHJBController(Controller):
         costs = (out["cost"] * valid).sum(0)
         return dict(records=records, average_trajectory_cost=float(costs.mean().item()),
                     average_trajectory_length=float((ds + 1).double().mean().item()), done_step=out["done_step"])
+
+    def _draw_start_states(self, ntraj: int) -> torch.Tensor:
+        """device_collection: this rank's `ntraj` rows of the start-state stream, and the stream advanced past every rank's share."""
+        x0 = self.dynamics.sample_initial_states(ntraj, seed=self.collection_seed, first_row=self.rows_drawn + self.rank * ntraj, dtype=self.dtype)
+        self.rows_drawn += ntraj * self.world_size
+        return x0
+
+    def _cost_stats(self, out):
+        """device_collection: (sum of the trajectory costs, sum of their squared deviations from the mean, number of tuples, B) of a rollout
+        log as four Python floats -- hjbx_rollout_cost_stats_* and its one read-back."""
+        _, stats = _ops.rollout_cost_stats(out["cost"], out["done_step"], want_traj_cost=True)
+        return stats.cpu().tolist()
 
     def _append_rollout(self, out) -> int:
         """`replay_buffer.xs.extend(trajectory)` for every trajectory of a rollout log (vhjb.py:304-308) -> the number of tuples it holds."""
@@ -904,7 +929,11 @@ class VHJBController(Controller):
             self.train_mode = False
             self.soft_pd_warmup = self.value_structure == "soft_pd" and epoch < self.soft_pd_warmup_epochs
             ntraj = self.num_of_trajectories_per_epoch
-            if ntraj > 0:
+            if ntraj > 0 and self.device_collection:
+                out = self.rollout_batch(self._draw_start_states(ntraj))
+                trajectory_lengths = self._append_rollout(out)
+                cost_sum, cost_dev2, _, _ = self._cost_stats(out)
+            elif ntraj > 0:
                 x0 = self._dev(self.dynamics.get_initial_state(batch_size=ntraj))
                 out = self.rollout_batch(x0)
                 ds = out["done_step"].long()
@@ -935,7 +964,11 @@ class VHJBController(Controller):
                     self.update_counter += 1
                     self.regularization = self.regularization_scheduler(self.update_counter)
 
-            if ntraj > 0:
+            if ntraj > 0 and self.device_collection:
+                average_trajectory_cost_list.append(cost_sum / ntraj)
+                std_trajectory_cost_list.append((cost_dev2 / ntraj) ** 0.5)
+                average_trajectory_length_list.append(trajectory_lengths / ntraj)
+            elif ntraj > 0:
                 average_trajectory_cost_list.append(float(traj_costs.sum() / ntraj))
                 std_trajectory_cost_list.append(float(np.var(traj_costs) ** 0.5))
                 average_trajectory_length_list.append(trajectory_lengths / ntraj)

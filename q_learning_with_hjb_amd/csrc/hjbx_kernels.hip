@@ -98,6 +98,24 @@ __global__ __launch_bounds__(kBlock) void k_initial_state(S sys, X0P<S, T> p, co
 }
 
 template <typename S, typename T>
+__global__ __launch_bounds__(kBlock) void k_initial_state_philox(S sys, X0P<S, T> p, uint64_t seed, uint64_t first_row, T* __restrict__ x0, int64_t B) {
+    k_initial_state_philox_body<S, T>(sys, p, seed, first_row, x0, B);
+}
+
+// The uniforms of k_initial_state_philox as a (B, n) buffer, for any n: what a user-defined system's hjbx_u_initial_state_* then reads
+// (its run-time compiled object gets no kernel of its own for this).  Same words, same conversion: philox_row_uniforms with a run-time n.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_philox_uniforms(uint64_t seed, uint64_t first_row, int n, T* __restrict__ u01, int64_t B) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= B) return;
+    T u[HJBX_MAX_N];
+    philox_row_uniforms<HJBX_MAX_N, T>(seed, first_row + (uint64_t)i, u);
+#pragma unroll
+    for (int k = 0; k < HJBX_MAX_N; ++k)
+        if (k < n) u01[i * n + k] = u[k];
+}
+
+template <typename S, typename T>
 __global__ __launch_bounds__(kBlock) void k_running_cost(S sys, TaskP<T, S::N, S::M> tk, const T* __restrict__ x,
                                                          const T* __restrict__ u, T* __restrict__ cost, int64_t B) {
     k_running_cost_body<S, T>(sys, tk, x, u, cost, B);
@@ -283,6 +301,52 @@ static int initial_state_impl(const hjbx_system* sys, const double* mean, const 
             hipLaunchKernelGGL((k_initial_state<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, p, u01, x0, B);
         })) return unsupported(sys);
     return check_launch("hjbx_initial_state");
+}
+
+// a (B, n) temporary in stream order: taken from and returned to the runtime's pool without stopping the host (the blocking pair is the
+// fall-back where the device has no pool)
+static hipError_t temp_alloc(void** p, size_t bytes, hipStream_t st, bool* pooled) {
+    *pooled = hipMallocAsync(p, bytes, st) == hipSuccess;
+    if (*pooled) return hipSuccess;
+    (void)hipGetLastError();
+    return hipMalloc(p, bytes);
+}
+static void temp_free(void* p, hipStream_t st, bool pooled) {
+    if (pooled && hipFreeAsync(p, st) == hipSuccess) return;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(p);
+}
+
+template <typename T>
+static int initial_state_philox_impl(const hjbx_system* sys, const double* mean, const double* sd, uint64_t seed, uint64_t first_row, T* x0,
+                                     int64_t B, void* st) {
+    HJBX_REQUIRE(sys != nullptr, "system handle is NULL");
+    HJBX_REQUIRE(B >= 0, "negative batch size %lld", (long long)B);
+    HJBX_REQUIRE(mean && sd, "x0_mean / x0_std are NULL");
+    HJBX_REQUIRE(x0 != nullptr || B == 0, "x0 is NULL");
+    if (B == 0) return HJBX_OK;
+    HJBX_CHECK_ROWS(x0, sys->n);
+    if (sys->kind == HJBX_SYS_USER) {
+        // two kernels: the library's uniforms into a temporary, then the handle's own hjbx_u_initial_state_* (the same body as the fused kernel)
+        void* tmp = nullptr;
+        bool pooled = false;
+        hipError_t e = temp_alloc(&tmp, (size_t)B * sys->n * sizeof(T), (hipStream_t)st, &pooled);
+        if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hjbx_initial_state_philox: %s", hipGetErrorString(e));
+        T* u01 = (T*)tmp;
+        hipLaunchKernelGGL((k_philox_uniforms<T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, seed, first_row, sys->n, u01, B);
+        int rc = check_launch("hjbx_initial_state_philox");
+        if (rc == HJBX_OK) rc = initial_state_impl<T>(sys, mean, sd, u01, x0, B, st);
+        temp_free(tmp, (hipStream_t)st, pooled);
+        return rc;
+    }
+    if (!with_system<T>(sys, [&](auto S) {
+            using SS = decltype(S);
+            X0P<SS, T> p;
+            for (int i = 0; i < SS::N; ++i) { p.mean[i] = (T)mean[i]; p.std[i] = (T)sd[i]; }
+            hipLaunchKernelGGL((k_initial_state_philox<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, p, seed, first_row, x0, B);
+        })) return unsupported(sys);
+    return check_launch("hjbx_initial_state_philox");
 }
 
 template <typename T>
@@ -630,5 +694,12 @@ int hjbx_dims(const hjbx_system* sys, int* n, int* m) {
 
 HJBX_DEFINE(float, f32)
 HJBX_DEFINE(double, f64)
+
+int hjbx_initial_state_philox_f32(const hjbx_system* s, const double* mean, const double* sd, uint64_t seed, uint64_t first_row, float* x0, int64_t B, void* st) {
+    return initial_state_philox_impl<float>(s, mean, sd, seed, first_row, x0, B, st);
+}
+int hjbx_initial_state_philox_f64(const hjbx_system* s, const double* mean, const double* sd, uint64_t seed, uint64_t first_row, double* x0, int64_t B, void* st) {
+    return initial_state_philox_impl<double>(s, mean, sd, seed, first_row, x0, B, st);
+}
 
 }  // extern "C"

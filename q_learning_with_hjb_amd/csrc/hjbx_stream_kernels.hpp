@@ -129,6 +129,18 @@ HJBX_DEV void k_simulate_body(S sys, Limits<T, S::M> lim, const T* x, const T* _
 
 template <typename S, typename T> struct X0P { T mean[S::N], std[S::N]; };
 
+// one start state from its n uniforms (dynamics_basic.py:28-29): the single statement of the arithmetic, shared by the kernel that
+// reads caller-supplied uniforms and the one that draws them itself (k_initial_state_philox_body), so the two cannot drift
+template <typename S, typename T>
+HJBX_DEV void initial_state_from_uniforms(const S& sys, const X0P<S, T>& p, const T* r, T* o) {
+#pragma unroll
+    for (int k = 0; k < S::N; ++k) {
+        const T lo = -p.std[k], hi = p.std[k];  // np.random.uniform(low, high): low + (high-low)*u
+        o[k] = (lo + (hi - lo) * r[k]) + p.mean[k];
+    }
+    sys.wrap(o);
+}
+
 template <typename S, typename T>
 HJBX_DEV void k_initial_state_body(S sys, X0P<S, T> p, const T* __restrict__ u01,
                                                           T* __restrict__ x0, int64_t B) {
@@ -136,12 +148,54 @@ HJBX_DEV void k_initial_state_body(S sys, X0P<S, T> p, const T* __restrict__ u01
     if (i >= B) return;
     T r[S::N], o[S::N];
     RowIO<T, S::N>::load(u01, i, r);
+    initial_state_from_uniforms<S, T>(sys, p, r, o);
+    RowIO<T, S::N>::store(x0, i, o);
+}
+
+// ----------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants): a
+// counter-based generator -- ten rounds of two 32x32->64 multiplies on a 128-bit counter under a 64-bit key, all in registers.
+// The start-state stream of include/hjbx.h: key = (lo32(seed), hi32(seed)), counter = (lo32(row), hi32(row), group, 0).
+// ----------------------------------------------------------------------------------------------
+struct Philox4 { uint32_t w[4]; };
+
+HJBX_DEV Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
-    for (int k = 0; k < S::N; ++k) {
-        const T lo = -p.std[k], hi = p.std[k];  // np.random.uniform(low, high): low + (high-low)*u
-        o[k] = (lo + (hi - lo) * r[k]) + p.mean[k];
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    sys.wrap(o);
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// the N uniforms in [0, 1) of row `row`: float32 takes one word per component (24 bits), float64 two (27 + 26 = 53 bits)
+template <int N, typename T> HJBX_DEV void philox_row_uniforms(uint64_t seed, uint64_t row, T* u) {
+    constexpr int PER = sizeof(T) == 4 ? 4 : 2;           // components per group of four words
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), r0 = (uint32_t)row, r1 = (uint32_t)(row >> 32);
+#pragma unroll
+    for (int g = 0; g < (N + PER - 1) / PER; ++g) {
+        const Philox4 x = philox4x32_10(r0, r1, (uint32_t)g, 0u, k0, k1);
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int k = g * PER + j;
+            if (k < N) {
+                if constexpr (sizeof(T) == 4) u[k] = (T)((float)(x.w[j] >> 8) * 0x1p-24f);
+                else u[k] = (T)((double)(((uint64_t)(x.w[2 * j] >> 5) << 26) + (uint64_t)(x.w[2 * j + 1] >> 6)) * 0x1p-53);
+            }
+        }
+    }
+}
+
+// start states drawn on the device: no u01 buffer, no generator state in memory; row i depends on (seed, first_row + i) only
+template <typename S, typename T>
+HJBX_DEV void k_initial_state_philox_body(S sys, X0P<S, T> p, uint64_t seed, uint64_t first_row, T* __restrict__ x0, int64_t B) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= B) return;
+    T r[S::N], o[S::N];
+    philox_row_uniforms<S::N, T>(seed, first_row + (uint64_t)i, r);
+    initial_state_from_uniforms<S, T>(sys, p, r, o);
     RowIO<T, S::N>::store(x0, i, o);
 }
 

@@ -140,6 +140,13 @@ class Dynamics:
         x0 = _ops.initial_state(self.system, self.x0_mean, self.x0_std, t).cpu().numpy()
         return x0[0] if batch_size is None else x0
 
+    def sample_initial_states(self, batch_size, seed, first_row=0, dtype=torch.float32, out=None):
+        """B start states of the same distribution as a (B, n) device tensor, drawn by the kernel itself: row i is a function of
+        (seed, first_row + i) alone (Philox4x32-10, the stream of include/hjbx.h), so it is reproducible and independent of the batch
+        size, of how a batch is split into calls, and of the rank that draws it.  Does not touch NumPy's or torch's generators and moves
+        nothing between host and device.  (`get_initial_state` keeps the reference's NumPy stream.)"""
+        return _ops.initial_state_philox(self.system, self.x0_mean, self.x0_std, batch_size, seed, first_row=first_row, dtype=dtype, out=out)
+
     def get_dimension(self) -> Tuple[int, int]:
         return self.state_dim, self.control_dim
 
