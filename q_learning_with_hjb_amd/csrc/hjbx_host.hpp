@@ -1,8 +1,9 @@
 // hjbx_host.hpp -- host-side conversion of the ABI descriptors (doubles) into the by-value kernel argument PODs and
-// the handle -> concrete device system dispatch.  Shared by hjbx_kernels.hip and hjbx_mlp.hip; not part of the ABI.
+// the handle -> concrete device system dispatch.  Shared by every translation unit that launches kernels; not part of the ABI.
 #pragma once
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 #include "hjbx_internal.hpp"
 #include "hjbx_systems.hpp"
@@ -88,6 +89,26 @@ template <typename T, typename F> inline bool with_system(const hjbx_system* s, 
     return false;
 }
 
+// a (B, cols) row-major buffer is accessed with its row's vector width (RowIO): 16, 8 or 4 bytes.  `least` = 7u for the state rows of the
+// matrix-core kernels, which read a row in pairs of floats at least
+inline bool aligned_rows(const void* p, size_t row_bytes, uintptr_t least = 3u) {
+    const uintptr_t a = (row_bytes % 16 == 0) ? 15u : (row_bytes % 8 == 0) ? 7u : least;
+    return (reinterpret_cast<uintptr_t>(p) & a) == 0;
+}
+
+// Calls f(integral_constant<int, n>, integral_constant<int, m>) for the (even) state and control dimension of a user-defined system whose
+// matrix-core kernels are enabled; `what` names the missing kernel otherwise
+template <typename F> inline int with_mc_dims(const hjbx_system* s, const char* who, const char* what, F&& f) {
+#define HJBX_UD(NN)                                                                                   \
+    case NN:                                                                                          \
+        if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
+        if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
+        if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
+        break;
+    switch (s->n) { HJBX_UD(2) HJBX_UD(4) HJBX_UD(6) HJBX_UD(8) HJBX_UD(10) }
+#undef HJBX_UD
+    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no %s for a user system with n=%d m=%d", who, what, s->n, s->m);
+}
 
 // Compute units of the CURRENT device (sizes the persistent grids and their workspaces); cached per device ordinal, not per process:
 // a process that moves to a second GPU must not size its launches with the first one's count.  0 = no device.

@@ -16,21 +16,35 @@ struct hjbx_system {
 int hjbx_user_launch(const hjbx_system* s, const char* kernel, unsigned grid, void** args, void* stream);
 void hjbx_user_release(void* user_program);
 
-// HJBX_SYS_USER handles that asked for the matrix-core kernels (hjbx_system_enable_matrix_cores): the network of either head as the two
-// launchers of hjbx_user.hip take it, and the launchers themselves -- called by the four C entry points of hjbx_mlp.hip / hjbx_softpd.hip
-// AFTER their argument checks; the first call for a (head, activation) compiles the kernels.  `who` names the entry point in messages.
-struct hjbx_user_net {
+// The value network of either head as every launcher of the two matrix-core kernels takes it (hjbx_mlp_host.hpp: make_net converts the ABI's
+// hjbx_mlp / hjbx_softpd_mlp, the shared argument checks and the launchers of the built-in systems read it; hjbx_user.hip: the launchers
+// of a user-defined system).
+struct hjbx_net {
     int soft, activation;                     // 0 = PD head (hjbx_mlp), 1 = soft-PD head (hjbx_softpd_mlp); hjbx_activation
+    int h1, h2, h3;                           // features
     const double *mean, *std, *xf;            // (n) each
     double eps_scalar;                        // PD head only (0 for the soft-PD head)
     const float *W1, *W2, *W3;                // device pointers
     const float *b1, *b2, *b3, *w4, *b4;      // soft-PD head only
 };
+// what a fused rollout takes after the descriptors, in the order of hjbx_vhjb_rollout_f32 / hjbx_softpd_rollout_f32
+struct hjbx_rollout_args {
+    int integrator, t_first, n_steps, T_max;
+    const float* x;
+    float *traj, *u_log, *cost, *done, *resid;
+    int32_t* done_step;
+    float* x_out;
+    const int32_t* env_order;
+    int64_t B;
+    void *workspace, *stream;
+};
+
+// HJBX_SYS_USER handles that asked for the matrix-core kernels (hjbx_system_enable_matrix_cores): the two launchers of hjbx_user.hip --
+// called by the four C entry points of hjbx_mlp.hip / hjbx_softpd.hip AFTER their argument checks; the first call for a (head, activation)
+// compiles the kernels.  `who` names the entry point in messages.
 bool hjbx_user_matrix_cores(const hjbx_system* s);
-int hjbx_user_value_grad(const hjbx_system* s, const hjbx_user_net* net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who);
-int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_user_net* net, int integrator, int t_first, int n_steps, int T_max,
-                      const float* x, float* traj, float* u_log, float* cost, float* done, float* resid, int32_t* done_step, float* x_out,
-                      const int32_t* env_order, int64_t B, void* workspace, void* stream, const char* who);
+int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who);
+int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& a, const char* who);
 
 // The parameter gradient of such a handle (hjbx_train_coop.hip calls both after the entry points' argument checks).  hjbx_user_train_unit:
 // the handle's train unit for `activation` (hjbx_user_train_kernels.hpp: k_train_coop<0|1, activation, 1|4, UserSystem<float>>), compiled now

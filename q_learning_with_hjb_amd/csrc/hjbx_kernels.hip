@@ -216,11 +216,6 @@ static int unsupported(const hjbx_system* s) {
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// a (B, cols) row-major buffer is accessed with RowIO's vector width: 16, 8 or 4 bytes
-static bool aligned_rows(const void* p, size_t row_bytes) {
-    const uintptr_t a = (row_bytes % 16 == 0) ? 15u : (row_bytes % 8 == 0) ? 7u : 3u;
-    return (reinterpret_cast<uintptr_t>(p) & a) == 0;
-}
 
 #define HJBX_CHECK_COMMON(sys, B)                                                   \
     HJBX_REQUIRE((sys) != nullptr, "system handle is NULL");                        \

@@ -33,6 +33,7 @@
 #include "hjbx_mlp_core.hpp"
 #include "hjbx_mlp_h2.hpp"
 #include "hjbx_adam.hpp"
+#include "hjbx_mlp_host.hpp"
 
 using namespace hjbx;
 
@@ -545,12 +546,10 @@ __global__ __launch_bounds__(256) void k_train_reduce(const float* __restrict__ 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-static int device_cus() { return hjbx_device_cus(); }   // per device ordinal (hjbx_host.hpp)
-
 struct TrainWs { size_t scratch, partial, sums, total; int64_t ntiles; int n_cu; };
 static TrainWs train_ws(int64_t B) {
     TrainWs w{};
-    w.n_cu = device_cus();
+    w.n_cu = hjbx_device_cus();
     if (w.n_cu <= 0) w.n_cu = 256;
     w.ntiles = (B + 31) / 32;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -568,13 +567,11 @@ static int launch_train(const hjbx_system* sysh, S sys, const hjbx_task* task, c
     if constexpr (N % 2 != 0 || N > 32) {
         return HJBX_EUNSUPPORTED;
     } else {
-        MlpP<N> p;
-        for (int k = 0; k < N; ++k) { p.mean[k] = (float)mlp->mean[k]; p.istd[k] = (float)(1.0 / mlp->std[k]); p.xf[k] = (float)mlp->xf[k]; }
-        p.eps_s = (float)mlp->eps_scalar;
+        const MlpP<N> p = make_mlp_params<N>(make_net(mlp));
         const auto tk = make_task<float, N, M>(task);
         const auto lim = make_limits<float, M>(sysh);
         const TrainWs w = train_ws(B);
-        if (device_cus() <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_value_loss_grad_f32: no HIP device");
+        if (hjbx_device_cus() <= 0) return hjbx_set_error(HJBX_ENODEVICE, "hjbx_value_loss_grad_f32: no HIP device");
         float* scratch = (float*)workspace;
         float* partial = (float*)((char*)workspace + w.scratch);
         double* sums = (double*)((char*)workspace + w.scratch + w.partial);
@@ -639,19 +636,13 @@ static int check_vlg(const char* who, const hjbx_system* sys, const hjbx_task* t
     if (B == 0) return HJBX_OK;
     if (!x || !cost || !done || !workspace || !mlp->W1 || !mlp->W2 || !mlp->W3)
         return hjbx_set_error(HJBX_EINVAL, "%s: x, cost, done, workspace and the weights must be non-NULL", who);
-    if (mlp->h1 != kH1 || mlp->h2 != kH2 || mlp->h3 != kH3)
-        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: features must be [128,128,64], got [%d,%d,%d]", who, mlp->h1, mlp->h2, mlp->h3);
-    if (mlp->activation != HJBX_ACT_RELU && mlp->activation != HJBX_ACT_TANH && mlp->activation != HJBX_ACT_SIN)
-        return hjbx_set_error(HJBX_EINVAL, "%s: unknown activation %d", who, mlp->activation);
-    const size_t row = (size_t)sys->n * sizeof(float);
-    const uintptr_t am = (row % 16 == 0) ? 15u : 7u;
-    if ((reinterpret_cast<uintptr_t>(x) & am) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+    const hjbx_net net = make_net(mlp);
+    if (int rc = check_features(who, net)) return rc;
+    if (!state_rows_aligned(x, sys) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return hjbx_set_error(HJBX_EINVAL, "%s: x must be aligned to its row vector width and workspace to 256 bytes", who);
     if ((reinterpret_cast<uintptr_t>(mlp->W1) | reinterpret_cast<uintptr_t>(mlp->W2) | reinterpret_cast<uintptr_t>(mlp->W3)) & 15u)
         return hjbx_set_error(HJBX_EINVAL, "%s: the weight matrices must be 16-byte aligned", who);
-    for (int k = 0; k < sys->n; ++k)
-        if (!(mlp->std[k] != 0.0)) return hjbx_set_error(HJBX_EINVAL, "%s: normalization_std[%d] is zero", who, k);
-    return HJBX_OK;
+    return check_std(who, net, sys->n);
 }
 
 // A user-defined system (hjbx_system_create_from_source) takes the cooperative kernel only, compiled for it at run time (hjbx_user.hip):
@@ -674,16 +665,12 @@ static int check_user_train(const char* who, const hjbx_system* sys) {
 static int run_pair(const hjbx_system* sys, const hjbx_task* task, const hjbx_mlp* mlp, int mode, const float* x, const float* cost, const float* done,
                     float* flat, void* workspace, int64_t B, void* stream) {
     int rc = HJBX_EUNSUPPORTED;
+    const bool ok = with_system<float>(sys, [&](auto S) {
 #ifdef HJBX_TRAIN_DEV   // development builds: cartpole only (the full set of instantiations takes minutes to compile)
-    bool ok = false;
-    if (sys->kind == HJBX_SYS_CARTPOLE) {
-        Cartpole<float> cp{(float)sys->p[0], (float)sys->p[1], (float)sys->p[2], (float)sys->p[3]};
-        rc = launch_train<Cartpole<float>>(sys, cp, task, mlp, mode, x, cost, done, flat, workspace, B, stream);
-        ok = true;
-    }
-#else
-    const bool ok = with_system<float>(sys, [&](auto S) { rc = launch_train<decltype(S)>(sys, S, task, mlp, mode, x, cost, done, flat, workspace, B, stream); });
+        if constexpr (std::is_same<decltype(S), Cartpole<float>>::value)
 #endif
+            rc = launch_train<decltype(S)>(sys, S, task, mlp, mode, x, cost, done, flat, workspace, B, stream);
+    });
     if (!ok || rc == HJBX_EUNSUPPORTED)
         return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_value_loss_grad_f32: no kernel for system kind %d with n=%d m=%d", sys->kind, sys->n, sys->m);
     return rc;

@@ -39,6 +39,7 @@
 #include "hjbx_mlp_core.hpp"
 #include "hjbx_adam.hpp"
 #include "hjbx_train_coop_kernels.hpp"
+#include "hjbx_mlp_host.hpp"
 
 using namespace hjbx;
 
@@ -212,9 +213,7 @@ static int launch_coop_nm(const hjbx_system* sysh, const hjbx_task* task, const 
             return hjbx_set_error(HJBX_EINVAL, "hjbx_value_loss_adam_f32: the Adam state's tensors must be W1 (%d x 128), W2 (128 x 128), W3 (128 x 64)", N);
         if (w.grid > kCoopMaxGrid) return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_value_loss_adam_f32: %d workgroups (more than %d CUs?)", w.grid, kCoopMaxGrid);
     }
-    MlpP<N> p;
-    for (int k = 0; k < N; ++k) { p.mean[k] = (float)mlp->mean[k]; p.istd[k] = (float)(1.0 / mlp->std[k]); p.xf[k] = (float)mlp->xf[k]; }
-    p.eps_s = (float)mlp->eps_scalar;
+    const MlpP<N> p = make_mlp_params<N>(make_net(mlp));
     const auto tk = make_task<float, N, M>(task);
     const auto lim = make_limits<float, M>(sysh);
     CoopCall c{(const float*)mlp->W1, (const float*)mlp->W2, (const float*)mlp->W3, x, cost, done, (float)task->eps, (float*)workspace,
@@ -274,7 +273,7 @@ static int launch_coop(const hjbx_system* sysh, S sys, const hjbx_task* task, co
 static int launch_coop_user(const hjbx_system* sysh, const hjbx_task* task, const hjbx_mlp* mlp, int mode, const float* x, const float* cost,
                             const float* done, float* flat, void* workspace, int64_t B, void* st, const FuseArgs* fuse, const char* who) {
     if (int rc = hjbx_user_train_unit(sysh, mlp->activation, who)) return rc;     // (before any launch; remembered when refused)
-    auto run = [&](auto Nc, auto Mc) -> int {
+    return with_mc_dims(sysh, who, "fused parameter gradient", [&](auto Nc, auto Mc) -> int {
         constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value;
         return launch_coop_nm<N, M>(sysh, task, mlp, x, cost, done, flat, workspace, B, st, fuse,
                                     [&](const CoopCall& c, const MlpP<N>& p, const TaskP<float, N, M>& tk, const Limits<float, M>& lim, hipStream_t s) -> int {
@@ -283,16 +282,7 @@ static int launch_coop_user(const hjbx_system* sysh, const hjbx_task* task, cons
                          (void*)&c.eps_term, (void*)&c.partial, (void*)&c.partial_w1, (void*)&c.sums, (void*)&c.B, (void*)&c.ntiles};
             return hjbx_user_train_launch(sysh, mlp->activation, mode == HJBX_RESIDUAL_NORMALISED ? 0 : 1, c.psplit, (unsigned)c.grid, a, s, who);
         });
-    };
-#define HJBX_UT_DIMS(NN)                                                                                 \
-    case NN:                                                                                             \
-        if (sysh->m == 1) return run(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
-        if (sysh->m == 2) return run(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
-        if (sysh->m == 3) return run(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
-        break;
-    switch (sysh->n) { HJBX_UT_DIMS(2) HJBX_UT_DIMS(4) HJBX_UT_DIMS(6) HJBX_UT_DIMS(8) HJBX_UT_DIMS(10) }
-#undef HJBX_UT_DIMS
-    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no fused parameter gradient for a user system with n=%d m=%d", who, sysh->n, sysh->m);
+    });
 }
 
 // called by hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 (hjbx_train.hip) after they have validated their arguments
@@ -303,20 +293,12 @@ int hjbx_train_coop(const hjbx_system* sys, const hjbx_task* task, const hjbx_ml
         return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the sin network's fused parameter gradient exists for n <= 4 (n = %d)", who, sys->n);
     if (sys->kind == HJBX_SYS_USER) return launch_coop_user(sys, task, mlp, mode, x, cost, done, flat, workspace, B, stream, fuse, who);
     int rc = HJBX_EUNSUPPORTED;
+    const bool ok = with_system<float>(sys, [&](auto S) {
 #ifdef HJBX_TRAIN_DEV   // development builds: cartpole and the 10-D quadcopter only
-    bool ok = false;
-    if (sys->kind == HJBX_SYS_CARTPOLE) {
-        Cartpole<float> cp{(float)sys->p[0], (float)sys->p[1], (float)sys->p[2], (float)sys->p[3]};
-        rc = launch_coop<Cartpole<float>>(sys, cp, task, mlp, mode, x, cost, done, flat, workspace, B, stream, fuse);
-        ok = true;
-    } else if (sys->kind == HJBX_SYS_NEARHOVER) {
-        NearHover<float> q{(float)sys->p[0], (float)sys->p[1], (float)sys->p[2], (float)sys->p[3]};
-        rc = launch_coop<NearHover<float>>(sys, q, task, mlp, mode, x, cost, done, flat, workspace, B, stream, fuse);
-        ok = true;
-    }
-#else
-    const bool ok = with_system<float>(sys, [&](auto S) { rc = launch_coop<decltype(S)>(sys, S, task, mlp, mode, x, cost, done, flat, workspace, B, stream, fuse); });
+        if constexpr (std::is_same<decltype(S), Cartpole<float>>::value || std::is_same<decltype(S), NearHover<float>>::value)
 #endif
+            rc = launch_coop<decltype(S)>(sys, S, task, mlp, mode, x, cost, done, flat, workspace, B, stream, fuse);
+    });
     if (!ok || rc == HJBX_EUNSUPPORTED)
         return hjbx_set_error(HJBX_EUNSUPPORTED, "hjbx_value_loss_grad_f32: no kernel for system kind %d with n=%d m=%d", sys->kind, sys->n, sys->m);
     return rc;

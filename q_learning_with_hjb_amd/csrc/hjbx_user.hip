@@ -131,7 +131,7 @@ struct UserUnit {
     // second call reports them again instead of compiling for another 20 s)
     int state = 0, status = HJBX_OK;
     std::string error, log;
-    std::string kernel[4];                           // symbols of: value gradient, Euler rollout, RK4 rollout (a train unit: kTrainKernels)
+    std::string kernel[4];                           // symbols of: value gradient, Euler rollout, RK4 rollout (a train unit: index = 2 * residual mode + (PS == 4))
 };
 
 struct UserProgram {
@@ -146,10 +146,6 @@ struct UserProgram {
     std::mutex train_mu;                             // guards the state of train[] (held across a lazy compile)
     UserUnit train[3];                               // [hjbx_activation]: the parameter-gradient unit (hjbx_user_train_kernels.hpp), PD head
 };
-
-// the four kernels of a train unit, in the order of UserUnit::kernel: index = 2 * residual mode + (PS == 4)
-const char* const kTrainKernels[4] = {"HJBX_UT_M0_PS1", "HJBX_UT_M0_PS4", "HJBX_UT_M1_PS1", "HJBX_UT_M1_PS4"};
-const char* const kTrainLabels[4] = {"k_train_coop<mode 0, PS 1>", "k_train_coop<mode 0, PS 4>", "k_train_coop<mode 1, PS 1>", "k_train_coop<mode 1, PS 4>"};
 
 // Compile `top` (one #include line) for the user's snippet with the library's own flags + `extra`; name expressions are resolved into
 // out->kernel[].  Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
@@ -260,30 +256,31 @@ void unload_unit(UserUnit& unit) {
         if (unit.mod[d]) (void)hipModuleUnload(unit.mod[d]);
 }
 
-// The matrix-core unit of an enabled handle for (head, activation), compiled now if this is the first call that needs it.
-int matrix_core_unit(const hjbx_system* s, int soft, int act, const char* who, UserUnit** out) {
-    UserProgram* u = s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
-    if (!u) return hjbx_set_error(HJBX_EINVAL, "%s: not a user-defined system", who);
-    if (soft < 0 || soft > 1 || act < 0 || act > 2) return hjbx_set_error(HJBX_EINVAL, "%s: unknown head %d / activation %d", who, soft, act);
-    std::lock_guard<std::mutex> lock(u->mc_mu);
-    if (!u->matrix_cores)
-        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
-    UserUnit& unit = u->mc[soft][act];
+// What a lazily compiled unit is made from, and how its refusal is worded
+struct UnitSpec {
+    const char *top, *name;                          // the one #include line, the unit's file name for hiprtc
+    std::vector<std::string> flags;                  // -D values beyond those of the handle
+    std::vector<const char*> kernels, labels;        // name expressions (resolved into UserUnit::kernel[]) and what the messages call them
+    std::string variant;                             // "activation 1, PD head": follows n and m in the scratch refusal
+    const char* budget;                              // what the kernels' code has to fit: ends the scratch refusal
+};
+
+// `unit` of handle `u`, compiled from make_spec() now if this is the first call that needs it (the caller holds the mutex of the unit's
+// state); every later call costs the state test alone: the spec, with its strings, is built for the compile only.
+// A kernel that needs scratch is a kernel that must not be launched: the whole unit is refused, its code object dropped, and the refusal
+// remembered with its status, message and compiler log.
+template <typename MakeSpec> int lazy_unit(UserProgram* u, UserUnit& unit, MakeSpec&& make_spec, const char* who, UserUnit** out) {
     if (unit.state == 0) {
+        const UnitSpec spec = make_spec();
         g_compile_log.clear();
         const Rtc& R = rtc();   // (loaded: the handle was created through it)
-        int rc = compile_unit(R, who, "#include \"hjbx_user_mlp_kernels.hpp\"\n", "hjbx_user_matrix_cores.hip", u->source, u->user_kind, u->n, u->m,
-                              u->np, {"-DHJBX_USER_MLP_ACT=" + std::to_string(act), "-DHJBX_USER_MLP_SOFT=" + std::to_string(soft)},
-                              {"HJBX_UM_VALUE_GRAD", "HJBX_UM_ROLLOUT_EULER", "HJBX_UM_ROLLOUT_RK4"}, &unit);
-        // Two waves per SIMD leave 256 registers per lane and the kernels keep a whole layer in them: a spill to scratch is a kernel that
-        // must not be launched (a spill store inside an EXEC-predicated region once produced wrong trajectories here)
-        for (int k = 0; rc == HJBX_OK && k < 3; ++k) {
+        int rc = compile_unit(R, who, spec.top, spec.name, u->source, u->user_kind, u->n, u->m, u->np, spec.flags, spec.kernels, &unit);
+        for (size_t k = 0; rc == HJBX_OK && k < spec.kernels.size(); ++k) {
             const long scratch = kernel_scratch_bytes(unit.code, unit.kernel[k]);
             if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, unit.kernel[k].c_str());
             else if (scratch > 0)
-                rc = hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the %s kernel of this user system (n=%d m=%d, activation %d, %s head) needs %ld bytes of "
-                                    "scratch: its code does not fit the 256 registers of the matrix-core kernels", who,
-                                    k == 0 ? "value-gradient" : k == 1 ? "Euler rollout" : "RK4 rollout", u->n, u->m, act, soft ? "soft-PD" : "PD", scratch);
+                rc = hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the %s kernel of this user system (n=%d m=%d, %s) needs %ld bytes of scratch: its code does not fit %s",
+                                    who, spec.labels[k], u->n, u->m, spec.variant.c_str(), scratch, spec.budget);
         }
         unit.state = rc == HJBX_OK ? 1 : -1;
         unit.status = rc;
@@ -303,6 +300,24 @@ int matrix_core_unit(const hjbx_system* s, int soft, int act, const char* who, U
     return HJBX_OK;
 }
 
+// The matrix-core unit of an enabled handle for (head, activation), compiled now if this is the first call that needs it.
+int matrix_core_unit(const hjbx_system* s, int soft, int act, const char* who, UserUnit** out) {
+    UserProgram* u = s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "%s: not a user-defined system", who);
+    if (soft < 0 || soft > 1 || act < 0 || act > 2) return hjbx_set_error(HJBX_EINVAL, "%s: unknown head %d / activation %d", who, soft, act);
+    std::lock_guard<std::mutex> lock(u->mc_mu);
+    if (!u->matrix_cores)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
+    // Two waves per SIMD leave 256 registers per lane and the kernels keep a whole layer in them: a spill to scratch is a kernel that
+    // must not be launched (a spill store inside an EXEC-predicated region once produced wrong trajectories here)
+    return lazy_unit(u, u->mc[soft][act], [&] { return
+                     UnitSpec{"#include \"hjbx_user_mlp_kernels.hpp\"\n", "hjbx_user_matrix_cores.hip",
+                              {"-DHJBX_USER_MLP_ACT=" + std::to_string(act), "-DHJBX_USER_MLP_SOFT=" + std::to_string(soft)},
+                              {"HJBX_UM_VALUE_GRAD", "HJBX_UM_ROLLOUT_EULER", "HJBX_UM_ROLLOUT_RK4"}, {"value-gradient", "Euler rollout", "RK4 rollout"},
+                              "activation " + std::to_string(act) + (soft ? ", soft-PD head" : ", PD head"), "the 256 registers of the matrix-core kernels"}; },
+                     who, out);
+}
+
 // The train unit of an enabled handle for `act`, compiled now if this is the first call that needs it.  One wave per SIMD and 512 registers:
 // when ANY of the four kernels needs scratch the whole unit is refused (a controller trains fused or it does not), the code object is
 // dropped and the refusal remembered; the handle keeps its streaming and rollout units.
@@ -317,39 +332,15 @@ int train_unit(const hjbx_system* s, int act, const char* who, UserUnit** out) {
     if (act == HJBX_ACT_SIN && s->n > 4)
         return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the sin network's fused parameter gradient exists for n <= 4 (n = %d)", who, s->n);
     std::lock_guard<std::mutex> lock(u->train_mu);
-    UserUnit& unit = u->train[act];
-    if (unit.state == 0) {
-        g_compile_log.clear();
-        const Rtc& R = rtc();   // (loaded: the handle was created through it)
-        // (the library's common flags only: with -fno-slp-vectorize, which hjbx_train_coop.hip's own build adds, hiprtc's compiler needs
-        //  16-72 bytes of scratch for the tanh / sin kernels of the test systems)
-        int rc = compile_unit(R, who, "#include \"hjbx_user_train_kernels.hpp\"\n", "hjbx_user_train.hip", u->source, u->user_kind, u->n, u->m, u->np,
-                              {"-DHJBX_USER_MLP_ACT=" + std::to_string(act)},
-                              {kTrainKernels[0], kTrainKernels[1], kTrainKernels[2], kTrainKernels[3]}, &unit);
-        for (int k = 0; rc == HJBX_OK && k < 4; ++k) {
-            const long scratch = kernel_scratch_bytes(unit.code, unit.kernel[k]);
-            if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, unit.kernel[k].c_str());
-            else if (scratch > 0)
-                rc = hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the %s kernel of this user system (n=%d m=%d, activation %d) needs %ld bytes of scratch: its "
-                                    "code does not fit the 512 registers of the cooperative parameter-gradient kernel; the fused parameter gradient "
-                                    "is refused for this system", who, kTrainLabels[k], u->n, u->m, act, scratch);
-        }
-        unit.state = rc == HJBX_OK ? 1 : -1;
-        unit.status = rc;
-        unit.log = g_compile_log;
-        if (rc != HJBX_OK) {
-            char msg[512];
-            hjbx_last_error(msg, sizeof msg);
-            unit.error = msg;
-            unit.code.clear();
-        }
-    }
-    if (unit.state < 0) {
-        g_compile_log = unit.log;
-        return hjbx_set_error(unit.status, "%s", unit.error.c_str());
-    }
-    *out = &unit;
-    return HJBX_OK;
+    // (the library's common flags only: with -fno-slp-vectorize, which hjbx_train_coop.hip's own build adds, hiprtc's compiler needs
+    //  16-72 bytes of scratch for the tanh / sin kernels of the test systems)
+    return lazy_unit(u, u->train[act], [&] { return
+                     UnitSpec{"#include \"hjbx_user_train_kernels.hpp\"\n", "hjbx_user_train.hip", {"-DHJBX_USER_MLP_ACT=" + std::to_string(act)},
+                              {"HJBX_UT_M0_PS1", "HJBX_UT_M0_PS4", "HJBX_UT_M1_PS1", "HJBX_UT_M1_PS4"},
+                              {"k_train_coop<mode 0, PS 1>", "k_train_coop<mode 0, PS 4>", "k_train_coop<mode 1, PS 1>", "k_train_coop<mode 1, PS 4>"},
+                              "activation " + std::to_string(act),
+                              "the 512 registers of the cooperative parameter-gradient kernel; the fused parameter gradient is refused for this system"}; },
+                     who, out);
 }
 }  // namespace
 
@@ -467,63 +458,47 @@ UserBlobF user_blob(const hjbx_system* s) {
     for (int i = 0; i < HJBX_USER_MAX_PARAMS; ++i) b.p[i] = i < s->n_params ? (float)s->p[i] : 0.f;
     return b;
 }
-MlpHeadSoft user_head(const hjbx_user_net* net) { return MlpHeadSoft{net->b1, net->b2, net->b3, net->w4, net->b4}; }
 constexpr unsigned kMcBlock = 8 * 64;   // WAVES * 64 of hjbx_user_mlp_kernels.hpp
-
-// calls f(integral_constant<int, n>, integral_constant<int, m>) for the (even) state and control dimension of an enabled handle
-template <typename F> int with_mc_dims(const hjbx_system* s, const char* who, F&& f) {
-#define HJBX_UD(NN)                                                                                   \
-    case NN:                                                                                          \
-        if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
-        if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
-        if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
-        break;
-    switch (s->n) { HJBX_UD(2) HJBX_UD(4) HJBX_UD(6) HJBX_UD(8) HJBX_UD(10) }
-#undef HJBX_UD
-    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no matrix-core kernel for a user system with n=%d m=%d", who, s->n, s->m);
-}
 }  // namespace
 
-int hjbx_user_value_grad(const hjbx_system* s, const hjbx_user_net* net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who) {
+int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who) {
     UserUnit* unit = nullptr;
-    if (int rc = matrix_core_unit(s, net->soft, net->activation, who, &unit)) return rc;
-    return with_mc_dims(s, who, [&](auto Nc, auto) -> int {
+    if (int rc = matrix_core_unit(s, net.soft, net.activation, who, &unit)) return rc;
+    return with_mc_dims(s, who, "matrix-core kernel", [&](auto Nc, auto) -> int {
         constexpr int N = decltype(Nc)::value;
         UserBlobF blob = user_blob(s);
-        MlpP<N> p = make_mlp_params<N>(net->mean, net->std, net->xf, net->eps_scalar);
+        MlpP<N> p = make_mlp_params<N>(net);
         int64_t ngroups = 0, grid = 0;
         if (int rc = mlp_value_grad_grid(B, 1, &ngroups, &grid, who)) return rc;
-        MlpHeadSoft soft = user_head(net);
+        MlpHeadSoft soft = make_head<MlpHeadSoft>(net);
         MlpHeadPd pd{};
-        void* a[] = {&blob, &p, (void*)&net->W1, (void*)&net->W2, (void*)&net->W3, (void*)&x, (void*)&V, (void*)&g, (void*)&B, &ngroups,
-                     net->soft ? (void*)&soft : (void*)&pd};
+        void* a[] = {&blob, &p, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&x, (void*)&V, (void*)&g, (void*)&B, &ngroups,
+                     net.soft ? (void*)&soft : (void*)&pd};
         return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[0].c_str(), (unsigned)grid, kMcBlock, a, stream, who);
     });
 }
 
-int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_user_net* net, int integrator, int t_first, int n_steps, int T_max,
-                      const float* x, float* traj, float* u_log, float* cost, float* done, float* resid, int32_t* done_step, float* x_out,
-                      const int32_t* order, int64_t B, void* workspace, void* stream, const char* who) {
-    if (integrator != HJBX_EULER && integrator != HJBX_RK4) return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: a user system steps with HJBX_EULER or HJBX_RK4", who);
+int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& r, const char* who) {
+    if (r.integrator != HJBX_EULER && r.integrator != HJBX_RK4) return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: a user system steps with HJBX_EULER or HJBX_RK4", who);
     UserUnit* unit = nullptr;
-    if (int rc = matrix_core_unit(s, net->soft, net->activation, who, &unit)) return rc;
-    return with_mc_dims(s, who, [&](auto Nc, auto Mc) -> int {
+    if (int rc = matrix_core_unit(s, net.soft, net.activation, who, &unit)) return rc;
+    return with_mc_dims(s, who, "matrix-core kernel", [&](auto Nc, auto Mc) -> int {
         constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value;
         UserBlobF blob = user_blob(s);
-        MlpP<N> p = make_mlp_params<N>(net->mean, net->std, net->xf, net->eps_scalar);
+        MlpP<N> p = make_mlp_params<N>(net);
         auto tk = make_task<float, N, M>(task);
         auto lim = make_limits<float, M>(s);
-        RolloutOut<N, M> o{traj, u_log, cost, done, resid, done_step, x_out};
+        RolloutOut<N, M> o{r.traj, r.u_log, r.cost, r.done, r.resid, r.done_step, r.x_out};
         int64_t ngroups = 0, grid = 0;
         int sched = 0;
-        if (int rc = mlp_rollout_grid(B, &ngroups, &grid, &sched, who)) return rc;
-        unsigned* ws = (unsigned*)workspace;
-        MlpHeadSoft soft = user_head(net);
+        if (int rc = mlp_rollout_grid(r.B, &ngroups, &grid, &sched, who)) return rc;
+        unsigned* ws = (unsigned*)r.workspace;
+        MlpHeadSoft soft = make_head<MlpHeadSoft>(net);
         MlpHeadPd pd{};
-        void* a[] = {&blob, &p, &tk, &lim, (void*)&net->W1, (void*)&net->W2, (void*)&net->W3, &t_first, &n_steps, &T_max, (void*)&x, (void*)&order,
-                     &o, (void*)&B, &ngroups, &ws, &sched, net->soft ? (void*)&soft : (void*)&pd};
-        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
-                           stream, who);
+        void* a[] = {&blob, &p, &tk, &lim, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&r.t_first, (void*)&r.n_steps, (void*)&r.T_max, (void*)&r.x,
+                     (void*)&r.env_order, &o, (void*)&r.B, &ngroups, &ws, &sched, net.soft ? (void*)&soft : (void*)&pd};
+        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[r.integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
+                           r.stream, who);
     });
 }
 

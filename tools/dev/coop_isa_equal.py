@@ -8,8 +8,12 @@ Every gfx950 code object is taken out of the two libraries' .hip_fatbin bundles,
 `builtin_instruction_streams` block of profiles/user_train.json); exit status 1 when a stream differs or a symbol of the first library is missing from the second
 (symbols only the second has are listed, not compared).
 
-    python tools/dev/coop_isa_equal.py <libhjbx.so of the parent commit> [<libhjbx.so of this tree>]
+--filter SUBSTRING (repeatable) compares the symbols whose name contains one of the substrings instead, e.g. k_value_grad_mfma,
+k_vhjb_rollout_mfma, k_train_ for a change of the host code around those kernels.
+
+    python tools/dev/coop_isa_equal.py [--filter SUBSTRING ...] <libhjbx.so of the parent commit> [<libhjbx.so of this tree>]
 """
+import argparse
 import hashlib
 import json
 import os
@@ -43,12 +47,12 @@ def code_objects(lib):
     return out
 
 
-def streams(lib):
-    """-> {symbol: (number of instructions, sha256 of the instruction text)} for the k_train_coop symbols of a library"""
+def streams(lib, filters=("k_train_coop",)):
+    """-> {symbol: (number of instructions, sha256 of the instruction text)} for the symbols of a library whose name contains a filter"""
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         for k, img in enumerate(code_objects(lib)):
-            if b"k_train_coop" not in img:
+            if not any(f.encode() in img for f in filters):
                 continue
             path = os.path.join(tmp, f"{k}.co")
             open(path, "wb").write(img)
@@ -56,17 +60,21 @@ def streams(lib):
             for line in subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", path], capture_output=True, text=True, check=True).stdout.splitlines():
                 m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
                 if m:
-                    body = res.setdefault(m.group(1), []) if "k_train_coop" in m.group(1) else None
+                    body = res.setdefault(m.group(1), []) if any(f in m.group(1) for f in filters) else None
                 elif body is not None and line.startswith("\t") and line.strip() != "...":     # ("...": objdump's elision of zero padding)
                     body.append(re.sub(r"\s+", " ", line.split("//")[0].strip()))
     return {name: (len(b), hashlib.sha256("\n".join(b).encode()).hexdigest()) for name, b in res.items() if b}
 
 
 def main():
-    if len(sys.argv) < 2:
-        raise SystemExit(__doc__)
-    before = streams(sys.argv[1])
-    after = streams(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "q_learning_with_hjb_amd", "csrc", "libhjbx.so"))
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("--filter", action="append", help="substring of the symbols to compare (default: k_train_coop)")
+    ap.add_argument("before")
+    ap.add_argument("after", nargs="?", default=os.path.join(ROOT, "q_learning_with_hjb_amd", "csrc", "libhjbx.so"))
+    args = ap.parse_args()
+    filters = tuple(args.filter or ("k_train_coop",))
+    before = streams(args.before, filters)
+    after = streams(args.after, filters)
     common = sorted(set(before) & set(after))
     differing = [n for n in common if before[n] != after[n]]
     missing = sorted(set(before) - set(after))
@@ -74,7 +82,7 @@ def main():
     main_kernels = [n for n in common if re.match(r"_Z12k_train_coopI", n)]
     ok = bool(common) and not differing and not missing
     print(json.dumps(dict(tool="tools/dev/coop_isa_equal.py", compared="llvm-objdump -d per symbol, instructions without addresses and encodings",
-                          symbols_compared=len(common), k_train_coop_instantiations=len(main_kernels),
+                          **({"filters": list(filters)} if args.filter else {}), symbols_compared=len(common), k_train_coop_instantiations=len(main_kernels),
                           instructions_compared=sum(after[n][0] for n in common), identical=ok, differing=differing, missing_after=missing,
                           added_after=added), indent=1))
     return 0 if ok else 1
