@@ -176,7 +176,8 @@ typedef struct hjbx_controller {
 typedef enum hjbx_activation {
     HJBX_ACT_RELU = 0, /* controller/vhjb.py:52,56 and examples/drone_hovering.ipynb, 10D_quadcopte.ipynb */
     HJBX_ACT_TANH = 1, /* examples/cartpole_balancing.ipynb cell 6 */
-    HJBX_ACT_SIN = 2   /* examples/double_integrator_optimal_time.ipynb cell 5 (sin and cos evaluated to ~1e-7 absolute, branch-free) */
+    HJBX_ACT_SIN = 2   /* examples/double_integrator_optimal_time.ipynb cell 5 (sin and cos evaluated to 1e-7 absolute for pre-activations
+                          |a| <= 1e3, bounded by 1 for every finite one: see hjbx_activation_probe_f32) */
 } hjbx_activation;
 
 /* Value network of controller/vhjb.py:17-60 (no bias, BatchNorm off): device weight pointers,
@@ -523,6 +524,21 @@ int hjbx_rollout_cost_stats_f32(const float* cost, const int32_t* done_step, int
                                 void* workspace, void* stream);
 int hjbx_rollout_cost_stats_f64(const double* cost, const int32_t* done_step, int64_t S, int64_t B, double* traj_cost, double* stats,
                                 void* workspace, void* stream);
+
+/* TEST INFRASTRUCTURE (like HJBX_OPT_ROLLOUT_EXTRA_WORKGROUPS): the element-wise activation functions that the matrix-core kernels inline,
+ * evaluated over a plain device array by the same device code, so that a test can sweep the whole float32 range against a float64 reference:
+ *   h[i] = act(a[i])                     (hjbx_activation: relu, tanh, sin)
+ *   s[i] = the factor act'(a[i]) in the form the kernels use: [h > 0] (relu) and 1 - h^2 (tanh), both taken from h; cos(a[i]) for sin.
+ * What the functions guarantee (asserted by tests/test_gpu_smooth_activations.py over every normal binade):
+ *   relu: exact, -0 and negative inputs give +0, NaN passes through (s = 0 for it);
+ *   tanh: relative error <= 6 x 2^-24 down to the smallest normal (<= 2 x 2^-24 for |a| < 0.625), odd bit for bit, +-1 exactly where the
+ *         float32 rounding of tanh is +-1, NaN for NaN;
+ *   sin / cos: absolute error <= 1e-7 for |a| <= 1e3 (sin relatively accurate as a -> 0); beyond that the accuracy decays (the argument
+ *         reduction uses two float32 constants) and is gone by |a| ~ 1e6, but every finite input gives |h|, |s| <= 1; NaN for NaN and +-inf.
+ * h or s may be NULL (not written).  One grid-stride launch on `stream`, no workspace.  HJBX_EINVAL before anything is enqueued: an unknown
+ * activation, N < 0, NULL a, a misaligned buffer.  N == 0 or both outputs NULL: HJBX_OK, nothing launched. */
+#define HJBX_HAS_ACTIVATION_PROBE 1 /* the entry point below exists (an addition, nothing else changed) */
+int hjbx_activation_probe_f32(int activation, const float* a, float* h, float* s, int64_t N, void* stream);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_fit.hip", (), "hjbx_fit.o"),
           ("hjbx_replay.hip", (), "hjbx_replay.o"),
           ("hjbx_collect.hip", (), "hjbx_collect.o"),
+          ("hjbx_probe.hip", (), "hjbx_probe.o"),                                 # test infrastructure: act1 / dact1 / sincos1 on a plain array
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=0",), "hjbx_softpd_relu.o"),    # soft-PD network: once per activation, like hjbx_mlp.hip
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=1",), "hjbx_softpd_tanh.o"),
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=2",), "hjbx_softpd_sin.o"),
@@ -252,7 +253,8 @@ EXPORTED_SYMBOLS = (
      "hjbx_value_loss_grad_workspace_bytes", "hjbx_value_loss_grad_f32", "hjbx_mix_gradients_f32", "hjbx_mix_adam_f32", "hjbx_replay_gather_f32",
      "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32", "hjbx_softpd_value_grad_f32", "hjbx_softpd_rollout_f32",
      "hjbx_replay_append_workspace_bytes", "hjbx_replay_append_f32", "hjbx_replay_append_f64",
-     "hjbx_initial_state_philox_f32", "hjbx_initial_state_philox_f64", "hjbx_rollout_cost_stats_f32", "hjbx_rollout_cost_stats_f64"]
+     "hjbx_initial_state_philox_f32", "hjbx_initial_state_philox_f64", "hjbx_rollout_cost_stats_f32", "hjbx_rollout_cost_stats_f64",
+     "hjbx_activation_probe_f32"]
     + [f"hjbx_{k}_{s}" for k in _typed_signatures() for s in ("f32", "f64")]
 )
 
@@ -334,6 +336,8 @@ def lib() -> C.CDLL:
             fn = getattr(L, f"hjbx_rollout_cost_stats_{sfx}")
             fn.restype = C.c_int
             fn.argtypes = [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP]
+        L.hjbx_activation_probe_f32.restype = C.c_int
+        L.hjbx_activation_probe_f32.argtypes = [_I32, _VP, _VP, _VP, _I64, _VP]
         for name, sig in _typed_signatures().items():
             for sfx in ("f32", "f64"):
                 fn = getattr(L, f"hjbx_{name}_{sfx}")

@@ -220,6 +220,17 @@ def rollout_cost_stats(cost, done_step, want_traj_cost=True):
     return traj_cost, stats
 
 
+def activation_probe(activation, a, want_h=True, want_s=True):
+    """hjbx_activation_probe_f32 (TEST INFRASTRUCTURE): the matrix-core kernels' own activation code on a flat float32 tensor `a` ->
+    (h = act(a), s = the derivative factor as the kernels form it: [h > 0], 1 - h^2, or the cosine next to the sine)."""
+    N = a.numel()
+    _chk(a, "a", (N,), torch.float32)
+    h = torch.empty_like(a) if want_h else None
+    s = torch.empty_like(a) if want_s else None
+    check(lib().hjbx_activation_probe_f32(_abi._ACTIVATIONS[activation], _p(a), _p(h), _p(s), N, _stream()))
+    return h, s
+
+
 def running_cost(sys, task, x, u):
     B = x.shape[0]
     _chk(x, "x", (B, sys.n))

@@ -35,23 +35,51 @@ __device__ __forceinline__ float relu1(float v) {
     return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
 
-// tanh for the notebooks' networks (hjbx_mlp.activation = HJBX_ACT_TANH): 1 - 2 / (exp(2x) + 1) on the hardware exp2 / rcp
-// units (5 VALU ops, two of them quarter rate); absolute error ~1e-7 over the whole range (exp2 overflow -> +1, underflow -> -1),
-// which is what matters for V = |y|^2 and its gradient.  The derivative comes from the value: 1 - tanh^2.
+// tanh for the notebooks' networks (hjbx_mlp.activation = HJBX_ACT_TANH), accurate in RELATIVE terms down to the smallest normal: a PD network
+// has no biases, so every pre-activation goes to zero with the error state, and V = |y|^2 and its gradient are only as good as tanh is
+// relative to its own size.  Two formulas, both always evaluated, chosen per element by a mask made with integer arithmetic:
+//   |x| >= 0.625: 1 - 2 / (exp(2|x|) + 1) on the hardware exp2 / rcp units (each good to 1 ulp).  Here tanh >= 0.55 and the subtraction
+//       from 1 amplifies the errors of the quotient by (1 - t) / t <= 0.81: relative error <= 6 x 2^-24 at the threshold, falling to the
+//       final rounding as |x| grows (exp2 overflow -> exactly 1);
+//   |x| <  0.625: the Cephes single-precision odd polynomial x + x z P(z), z = x^2 (approximation error 0.15 x 2^-24; the correction term
+//       is at most 0.13 |x|, so its roundings hardly count): relative error <= 2 x 2^-24, and subnormal inputs come back unchanged.
+// 1 - 2 / (exp(2x) + 1) alone, the earlier form, rounds exp(2x) + 1 at ulp(2): 6e-8 of ABSOLUTE error whatever x is, and exactly 0 below 3e-8.
+// The exp2 formula runs on |x| and the sign of x is copied onto the result, so tanh1(-x) == -tanh1(x) bit for bit.  NaN gives NaN.
+// The choice is written as a mask, the sign of an integer difference of the bit patterns (|x| < 0.625 <=> bits(|x|) < 0x3f200000; NaN and inf
+// take the exp2 side); hipcc makes one integer v_cmp + v_cndmask of it, consumed at once -- unlike the three compares per element that sincos1
+// avoids, it left no lane mask alive in any instantiation (zero scratch, no spilled register: the audits of tests/).  15 VALU ops, two of them
+// quarter rate, three registers live at most; the one kernel that has not got them (the parameter gradient of a user system with n > 4, at
+// 498 of 512 VGPRs) fences its evaluations one by one (hjbx_train_coop_kernels.hpp).  The derivative comes from the value: 1 - tanh^2.
 __device__ __forceinline__ float tanh1(float v) {
-    const float ex = __builtin_amdgcn_exp2f(v * 2.8853900817779268f);  // exp(2x) = 2^(2x log2 e)
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(ex + 1.0f);
+    const float z = v * v;
+    float p = fmaf(-5.70498872745e-3f, z, 2.06390887954e-2f);
+    p = fmaf(p, z, -5.37397155531e-2f);
+    p = fmaf(p, z, 1.33314422036e-1f);
+    p = fmaf(p, z, -3.33332819422e-1f);
+    const float small = fmaf(p * z, v, v);
+    const uint32_t uv = __builtin_bit_cast(uint32_t, v), ua = uv & 0x7fffffffu;
+    const float ex = __builtin_amdgcn_exp2f(__builtin_bit_cast(float, ua) * 2.8853900817779268f);  // exp(2|x|) = 2^(2|x| log2 e)
+    const float big = 1.0f - 2.0f * __builtin_amdgcn_rcpf(ex + 1.0f);
+    const uint32_t m = (uint32_t)((int32_t)(ua - 0x3f200000u) >> 31);  // all ones below the threshold
+    const uint32_t r = (__builtin_bit_cast(uint32_t, small) & m) | (__builtin_bit_cast(uint32_t, big) & ~m);
+    return __builtin_bit_cast(float, (r & 0x7fffffffu) | (uv & 0x80000000u));
 }
 // sin / cos for the time-optimal notebook's network (hjbx_mlp.activation = HJBX_ACT_SIN), branch-free and without the stack frame of the
 // library's large-argument path (the matrix-core kernels must stay free of scratch): k = rint(x 2/pi), r = x - k pi/2 by a two-constant
 // Cody-Waite reduction under fma (exact for |k| < 2^12 or so: pre-activations are O(1) to O(100)), the Cephes single-precision minimax
-// polynomials on [-pi/4, pi/4] (about 1 ulp), quadrant by bit operations.  Absolute error ~1e-7 for |x| < 1e3.
+// polynomials on [-pi/4, pi/4] (about 1 ulp), quadrant by bit operations.  Absolute error <= 1e-7 for |x| <= 1e3, sin relatively accurate
+// as x -> 0.  Beyond 1e3 the two constants no longer reduce exactly: the error grows with |x| (1e-7 still at 1e5, nothing left of the
+// phase from ~1e6), and once k is no integer-accurate float (|x| > ~5e7) r is not reduced at all -- so r is held to +-0.8125 (one v_med3;
+// inside the domain |r| <= pi/4 + 1e-4 and nothing changes, bit for bit), which bounds both polynomials by 1: EVERY finite x gives
+// |sin|, |cos| <= 1, where the bare polynomials returned 85 at 1e8 and inf from 1e13.  v_med3 drops a NaN (it answers with the minimum of
+// the other two), so the NaN of a non-finite x (r = inf - inf) is put back into r^2 through r * 0: NaN and +-inf give NaN.
 __device__ __forceinline__ void sincos1(float x, float& sn, float& cs) {
     const float k = rintf(x * 0.63661977236758134f);
     float r = fmaf(k, -1.5707963705062866f, x);
     r = fmaf(k, 4.371139000186243e-08f, r);
-    const float r2 = r * r;
-    const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, r2, 8.3321608736e-3f), r2, -1.6666654611e-1f) * r2, r, r);
+    const float rc = __builtin_amdgcn_fmed3f(r, -0.8125f, 0.8125f);
+    const float r2 = fmaf(rc, rc, r * 0.0f);
+    const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, r2, 8.3321608736e-3f), r2, -1.6666654611e-1f) * r2, rc, rc);
     const float pc = fmaf(fmaf(fmaf(2.443315711809948e-5f, r2, -1.388731625493765e-3f), r2, 4.166664568298827e-2f), r2 * r2, fmaf(-0.5f, r2, 1.0f));
     // quadrant without compares (a compare per element becomes an SGPR lane mask; 64 elements x 3 of them spill): odd k swaps the two
     // polynomials through a bit-field insert under an all-ones / all-zeros mask, bits 1 of k and k + 1 go straight into the sign bits

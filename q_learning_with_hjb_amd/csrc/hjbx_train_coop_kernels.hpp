@@ -333,6 +333,12 @@ __global__ __launch_bounds__(256, 1) void k_train_coop(S sys_k, MlpP<S::N> p_k, 
                 s1r[r] = cs;
             } else {
                 h1r[r] = act1<ACT>(t[0][0][r]);
+#ifdef HJBX_USER_TRAIN_UNIT
+                if constexpr (ACT == HJBX_ACT_TANH && N > 4) {   // one tanh at a time: its two formulas interleaved over 16 elements cost hiprtc 4 spilled VGPRs here
+                    asm volatile("" : "+v"(h1r[r]));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#endif
             }
         }
         auto dmul1 = [&](int r, float v) __attribute__((always_inline)) { if constexpr (SIN) return v * s1r[r]; else return dact1<ACT>(h1r[r], v); };
@@ -381,6 +387,12 @@ __global__ __launch_bounds__(256, 1) void k_train_coop(S sys_k, MlpP<S::N> p_k, 
                 s2r[r] = cs;
             } else {
                 h2r[r] = act1<ACT>(acc[r]);
+#ifdef HJBX_USER_TRAIN_UNIT
+                if constexpr (ACT == HJBX_ACT_TANH && N > 4) {   // one tanh at a time: its two formulas interleaved over 16 elements cost hiprtc 4 spilled VGPRs here
+                    asm volatile("" : "+v"(h2r[r]));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#endif
             }
         }
         auto dmul2 = [&](int r, float v) __attribute__((always_inline)) { if constexpr (SIN) return v * s2r[r]; else return dact1<ACT>(h2r[r], v); };
