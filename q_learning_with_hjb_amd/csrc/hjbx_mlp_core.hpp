@@ -290,6 +290,57 @@ template <int N> __device__ __forceinline__ MlpCtx mlp_ctx(MlpLds<N>& L, int lan
     return c;
 }
 
+// ---- shared by the two split-operand arithmetics (hjbx_mlp_x3.hpp: bf16x3, hjbx_mlp_h2.hpp: f16x2) -------------------------------------
+// Their swizzled 16-bit weight images (layout: top of hjbx_mlp_x3.hpp), the two kinds of LDS read on them, and the ReLU masks.
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+static constexpr int kImgRow = 256;               // bytes per image row: 128 input features x 2 B
+static constexpr int kImgPiece = 64 * kImgRow;    // one piece of 64 rows
+__host__ __device__ constexpr int img_sw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+
+template <int BYTE_OFF> __device__ __forceinline__ u32x2 lds_read_b64(uint32_t addr) {
+    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 8 == 0, "");
+    u32x2 v;
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(BYTE_OFF));
+    return v;
+}
+// EXEC must be all ones (the gather crosses lanes): the chains run with every lane active, padding lanes included
+template <int BYTE_OFF> __device__ __forceinline__ u32x2 lds_read_tr16_b64(uint32_t addr) {
+    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 8 == 0, "");
+    u32x2 v;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(BYTE_OFF));
+    return v;
+}
+
+// ReLU derivatives as bit masks (128 bits per lane and layer: bit 16 (fb & 1) + r of m[fb >> 1] belongs to register r of block fb)
+// v = relu(v) and bit BIT of m = [v > 0]
+template <int BIT> __device__ __forceinline__ void relu_mask(float& v, uint32_t& m) {
+    v = relu1(v);
+    uint32_t t;
+    asm("v_min_u32_e32 %0, 1, %2\n\tv_lshl_or_b32 %1, %0, %3, %1" : "=&v"(t), "+v"(m) : "v"(v), "n"(BIT));
+}
+// x * [bit BIT of m]
+template <int BIT> __device__ __forceinline__ float mask_apply(float x, uint32_t m) {
+    float y;
+    asm("v_bfe_i32 %0, %1, %2, 1\n\tv_and_b32_e32 %0, %0, %3" : "=&v"(y) : "v"(m), "n"(BIT), "v"(x));
+    return y;
+}
+
+// What happens to the chain's input registers on their way into the B fragments (PRE): the element-wise work between two products runs
+// inside the consuming chain, two elements per unit next to their split, instead of in a VALU-only pass in front of it (where this
+// wave issues no MFMA for ~500 instructions and relies on its SIMD partner being inside a chain at that moment).
+enum { kPreNone = 0, kPreReluMask = 1, kPreMaskApply = 2 };  // relu + record [v > 0] in the mask | multiply by the recorded mask bit
+
+template <int FB, int R> __device__ __forceinline__ void mask_apply_block(f32x16 (&a)[4], const uint32_t (&m)[2]) {
+    if constexpr (FB < 4) {
+        const float v = a[FB][R];
+        a[FB][R] = mask_apply<16 * (FB & 1) + R>(v, m[FB >> 1]);
+        if constexpr (R + 1 < 16) mask_apply_block<FB, R + 1>(a, m);
+        else mask_apply_block<FB + 1, 0>(a, m);
+    }
+}
+
 // V and dV/dx of the TL tiles whose state rows are in xs (one environment per lane, identical in both lane
 // halves).  On return every lane holds its environment's V and (if want_grad) gradient.
 // SOFT selects the head: false (PD, controller/vhjb.py) V = |y|^2 + eps_s |e|^2, dV/dy = 2y;  true (soft-PD, `bias` = the LDS copy of
@@ -513,3 +564,48 @@ template <int N> __device__ __forceinline__ void store_row(float* __restrict__ o
     }
 }
 
+// One sample of a tile for its lane: the state row, or the target state xf for a padding lane (`ok` false: a tile group beyond the range or an
+// environment beyond B; such a lane computes like any other and emits nothing) ...
+template <int N> __device__ __forceinline__ void load_sample(const float* x, const MlpP<N>& p, int64_t env, bool ok, float (&xv)[N]) {
+    if (ok) load_row<N>(x, env, xv);
+    else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) xv[k] = p.xf[k];
+    }
+}
+// ... and, for the parameter-gradient kernels, its done flag (padding: 0) and cost (padding: 1)
+template <int N>
+__device__ __forceinline__ void load_sample(const float* x, const float* cost, const float* done, const MlpP<N>& p, int64_t env, bool ok, float (&xv)[N],
+                                            float& dn, float& cst) {
+    load_sample<N>(x, p, env, ok, xv);
+    dn = ok ? done[env] : 0.f;
+    cst = ok ? cost[env] : 1.f;
+}
+
+// ---- partial sums of 32x32 MFMA accumulator blocks (the parameter-gradient kernels and their epilogues) ----------------------------------
+// A workgroup's record is the raw accumulator layout [block][register][lane]; the epilogue kernels take one thread per element and invert it
+// (row = perm(register) + 4 (lane >> 5), column = lane & 31 of the block).
+__device__ __forceinline__ void put_acc_block(float* out, int blk, int lane, const f32x16& a) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[blk * 1024 + r * 64 + lane] = a[r];
+}
+
+// ---- the arithmetic of the 128 / 64-wide products (HJBX_OPT_MLP_ARITHMETIC) as the kernels see it ----------------------------------------
+// MlpArith<AR>: the LDS image of the weights, its fill (every thread of the workgroup calls it; a __syncthreads() follows), the lane context
+// made from it and the value gradient of one tile group.  AR = 0: f32 MFMA (here), 1: bf16x3 (hjbx_mlp_x3.hpp), 2: f16x2 (hjbx_mlp_h2.hpp);
+// the split-operand arithmetics hold one tile per wave and exist for the ReLU network.  The soft-PD head (f32 MFMA only) stays with the
+// kernels' HEAD parameter.
+template <int AR> struct MlpArith;
+template <> struct MlpArith<0> {
+    template <int N> using Lds = MlpLds<N>;
+    template <int N, int THREADS>
+    static __device__ __forceinline__ void fill(Lds<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g, const float* __restrict__ W3g, int tid) {
+        mlp_fill_lds<N, THREADS>(L, W1g, W2g, W3g, tid);
+    }
+    template <int N> static __device__ __forceinline__ MlpCtx ctx(Lds<N>& L, int lane) { return mlp_ctx<N>(L, lane); }
+    template <typename S, int TL, int ACT>
+    static __device__ __forceinline__ void value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtx& c, const float (&xs)[TL][S::N], bool want_grad,
+                                                      float (&V)[TL], float (&g)[TL][S::N]) {
+        mlp_value_grad<S, TL, ACT>(sys, p, c, xs, want_grad, V, g);
+    }
+};

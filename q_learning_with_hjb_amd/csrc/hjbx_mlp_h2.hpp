@@ -21,7 +21,7 @@
 // Layout, chain structure, masks: as hjbx_mlp_x3.hpp (one swizzled [output][input] image per piece, row reads forward, transposed reads
 // backward, element-wise work inside the consuming chain).
 #pragma once
-#include "hjbx_mlp_x3.hpp"
+#include "hjbx_mlp_core.hpp"
 
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
@@ -88,10 +88,29 @@ template <int NO, int THREADS> __device__ __forceinline__ void h2_fill_image(uns
     }
 }
 
+struct MlpCtxH2 {
+    uint32_t w1f;
+    const float4* w1t;
+    int i, h;
+    uint32_t f2, f3, t2, t3;  // lane bases: row reads / transposed reads of the W2 and W3 images
+    int kw2, kw3;
+};
+
+// the f16x2 arithmetic as the kernels see it (MlpArith: hjbx_mlp_core.hpp); the members are defined below, where their code has always been
+template <> struct MlpArith<2> {
+    template <int N> using Lds = MlpLdsH2<N>;
+    template <int N, int THREADS>
+    static __device__ void fill(MlpLdsH2<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g, const float* __restrict__ W3g, int tid);
+    template <int N> static __device__ MlpCtxH2 ctx(MlpLdsH2<N>& L, int lane);
+    template <typename S, int TL, int ACT>
+    static __device__ void value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtxH2& c, const float (&xs)[TL][S::N], bool want_grad, float (&V)[TL],
+                                      float (&g)[TL][S::N]);
+};
+
 // NOTE: contains two __syncthreads(): every thread of the workgroup must call it
 template <int N, int THREADS>
-__device__ __forceinline__ void mlp_fill_lds_h2(MlpLdsH2<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g,
-                                                const float* __restrict__ W3g, int tid) {
+__device__ __forceinline__ void MlpArith<2>::fill(MlpLdsH2<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g,
+                                                  const float* __restrict__ W3g, int tid) {
     constexpr int NP = MlpLdsH2<N>::NP;
     if (tid < 2) L.wmax[tid] = 0u;
     __syncthreads();
@@ -109,16 +128,8 @@ __device__ __forceinline__ void mlp_fill_lds_h2(MlpLdsH2<N>& L, const float* __r
     if (tid == 0) { L.kw[0] = k2; L.kw[1] = k3; }
 }
 
-struct MlpCtxH2 {
-    uint32_t w1f;
-    const float4* w1t;
-    int i, h;
-    uint32_t f2, f3, t2, t3;  // lane bases: row reads / transposed reads of the W2 and W3 images
-    int kw2, kw3;
-};
-
-// (call after the barrier that follows mlp_fill_lds_h2)
-template <int N> __device__ __forceinline__ MlpCtxH2 mlp_ctx_h2(MlpLdsH2<N>& L, int lane) {
+// (call after the barrier that follows fill)
+template <int N> __device__ __forceinline__ MlpCtxH2 MlpArith<2>::ctx(MlpLdsH2<N>& L, int lane) {
     constexpr int NP = MlpLdsH2<N>::NP;
     MlpCtxH2 c;
     c.i = lane & 31;
@@ -259,9 +270,10 @@ template <int NB> __device__ __forceinline__ void zero_blocks(f32x16 (&a)[NB]) {
 }
 
 // V and dV/dx of one tile of 32 environments (ReLU network); same contract as mlp_value_grad with TL = 1
-template <typename S>
-__device__ __forceinline__ void mlp_value_grad_h2(const S& sys, const MlpP<S::N>& p, const MlpCtxH2& c, const float (&xs)[1][S::N], bool want_grad,
-                                                  float (&V)[1], float (&g)[1][S::N]) {
+template <typename S, int TL, int ACT>
+__device__ __forceinline__ void MlpArith<2>::value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtxH2& c, const float (&xs)[TL][S::N], bool want_grad,
+                                                        float (&V)[TL], float (&g)[TL][S::N]) {
+    static_assert(TL == 1 && ACT == HJBX_ACT_RELU, "f16x2: one tile per wave, ReLU network");
     constexpr int N = S::N;
     constexpr int NP = MlpLdsH2<N>::NP;
     const int h = c.h;

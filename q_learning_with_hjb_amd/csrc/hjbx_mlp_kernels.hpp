@@ -15,12 +15,10 @@
 
 using namespace hjbx;
 
-template <int N, int AR> using MlpLdsT = std::conditional_t<AR == 1, MlpLdsX3<N>, std::conditional_t<AR == 2, MlpLdsH2<N>, MlpLds<N>>>;
-
 // The head of the network (mlp_value_grad's SOFT) and what it adds to the kernels' arguments and LDS image.
 struct MlpHeadPd {   // V = |y|^2 + eps_s |e|^2 (controller/vhjb.py:17-60): nothing beyond the three weight matrices
     static constexpr bool kSoft = false;
-    template <int N, int AR> using Lds = MlpLdsT<N, AR>;
+    template <int N, int AR> using Lds = typename MlpArith<AR>::template Lds<N>;
 };
 struct MlpHeadSoft {  // V = act(a3) . w4 + b4 with biases on every layer (SoftPDValueApproximator of the notebooks); f32 MFMA only
     static constexpr bool kSoft = true;
@@ -43,17 +41,13 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_value_grad_mfma(S sys
 #ifdef HJBX_DIAG_CLOCK
     const unsigned long long tentry = __builtin_amdgcn_s_memrealtime();
 #endif
-    if constexpr (AR == 1) mlp_fill_lds_x3<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
-    else if constexpr (AR == 2) mlp_fill_lds_h2<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
-    else mlp_fill_lds<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
+    MlpArith<AR>::template fill<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
     if constexpr (HEAD::kSoft) mlp_fill_bias<WAVES * 64>(L.bias, head.b1, head.b2, head.b3, head.w4, head.b4, tid);
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
-    const auto c = [&] {
-        if constexpr (AR == 1) return mlp_ctx_x3<N>(L, lane);
-        else if constexpr (AR == 2) return mlp_ctx_h2<N>(L, lane);
-        else return mlp_ctx<N>(L, lane);
-    }();
+    // (the context is made inside a lambda, here and in the other kernels: called directly, hipcc forms the lane bases of the swizzled images
+    //  with other instructions than it has so far)
+    const auto c = [&] { return MlpArith<AR>::template ctx<N>(L, lane); }();
     const int i = c.i, h = c.h;
 
     // Work distribution: the workgroup owns a contiguous range of tile groups and its waves pull the next one
@@ -68,12 +62,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_value_grad_mfma(S sys
 #pragma unroll
         for (int t = 0; t < TL; ++t) {
             const int64_t en = (grp * TL + t) * 32 + i;
-            if (grp < g_end && en < B) {
-                load_row<N>(x, en, dst[t]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < N; ++k) dst[t][k] = p.xf[k];
-            }
+            load_sample<N>(x, p, en, grp < g_end && en < B, dst[t]);
         }
     };
 
@@ -94,10 +83,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_value_grad_mfma(S sys
         load_rows(grp_next, xn);
 
         float V[TL], g[TL][N];
-        if constexpr (AR == 1) mlp_value_grad_x3<S>(sys, p, c, xs, gout != nullptr, V, g);
-        else if constexpr (AR == 2) mlp_value_grad_h2<S>(sys, p, c, xs, gout != nullptr, V, g);
-        else if constexpr (HEAD::kSoft) mlp_value_grad<S, TL, ACT, true>(sys, p, c, xs, gout != nullptr, V, g, &L.bias);
-        else mlp_value_grad<S, TL, ACT>(sys, p, c, xs, gout != nullptr, V, g);
+        if constexpr (HEAD::kSoft) mlp_value_grad<S, TL, ACT, true>(sys, p, c, xs, gout != nullptr, V, g, &L.bias);
+        else MlpArith<AR>::template value_grad<S, TL, ACT>(sys, p, c, xs, gout != nullptr, V, g);
 #pragma unroll
         for (int t = 0; t < TL; ++t) {
             const int64_t env = (grp * TL + t) * 32 + i;
@@ -186,9 +173,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_vhjb_rollout_mfma(S s
         __hip_atomic_fetch_add(ws + kWsStarted, 1u, HJBX_RLX_AGENT);
         sys_s = sys_k; p_s = p_k; tk_s = tk_k; lim_s = lim_k;
     }
-    if constexpr (AR == 1) mlp_fill_lds_x3<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
-    else if constexpr (AR == 2) mlp_fill_lds_h2<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
-    else mlp_fill_lds<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
+    MlpArith<AR>::template fill<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
     if constexpr (HEAD::kSoft) mlp_fill_bias<WAVES * 64>(L.bias, head.b1, head.b2, head.b3, head.w4, head.b4, tid);
     __syncthreads();
     const S& sys = sys_s;
@@ -202,11 +187,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_vhjb_rollout_mfma(S s
     // produced wrong trajectories).  A CPU test also keeps every instantiation at zero scratch.
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned my_flag_u = (unsigned)__builtin_amdgcn_readfirstlane((int)my_flag);
-    const auto c = [&] {
-        if constexpr (AR == 1) return mlp_ctx_x3<N>(L, lane);
-        else if constexpr (AR == 2) return mlp_ctx_h2<N>(L, lane);
-        else return mlp_ctx<N>(L, lane);
-    }();
+    const auto c = [&] { return MlpArith<AR>::template ctx<N>(L, lane); }();
     const int i = c.i, h = c.h;
     const int simd = wave & 3;
     const int G = (int)gridDim.x;
@@ -297,10 +278,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_vhjb_rollout_mfma(S s
                 cst = dn = res = 0.0f;
             } else {
                 float V[1], g[1][N];
-                if constexpr (AR == 1) mlp_value_grad_x3<S>(sys, p, c, xs, true, V, g);
-                else if constexpr (AR == 2) mlp_value_grad_h2<S>(sys, p, c, xs, true, V, g);
-                else if constexpr (HEAD::kSoft) mlp_value_grad<S, 1, ACT, true>(sys, p, c, xs, true, V, g, &L.bias);
-                else mlp_value_grad<S, 1, ACT>(sys, p, c, xs, true, V, g);
+                if constexpr (HEAD::kSoft) mlp_value_grad<S, 1, ACT, true>(sys, p, c, xs, true, V, g, &L.bias);
+                else MlpArith<AR>::template value_grad<S, 1, ACT>(sys, p, c, xs, true, V, g);
                 vhjb_step_env<INTEG>(sys, tk, lim, t_first + k, T_max, o.resid != nullptr, xs[0], g[0], ds, xo, u, cst, dn, res);
             }
             if (writer) {

@@ -27,18 +27,13 @@
 #include "hjbx_mlp_core.hpp"
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
 
-static constexpr int kImgRow = 256;               // bytes per image row: 128 input features x 2 B
-static constexpr int kImgPiece = 64 * kImgRow;    // one piece of 64 rows
 static constexpr int kImgHalf = 3 * kImgPiece;    // [piece][64 rows]: everything a lane base + 16-bit offset field has to reach
 static constexpr int kW2Img = 2 * kImgHalf;       // 128 output features
 static constexpr int kW3Img = kImgHalf;           // 64 output features
 
-__host__ __device__ constexpr int img_sw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 // byte offset of the 8-byte slot that holds input features 4 c4 .. 4 c4 + 3 of output feature `row`, piece `piece`
 __host__ __device__ constexpr int img_off(int piece, int row, int c4) {
     return (row >> 6) * kImgHalf + piece * kImgPiece + (row & 63) * kImgRow + 16 * ((c4 >> 1) ^ img_sw(row)) + 8 * ((c4 & 1) ^ ((row >> 4) & 1));
@@ -84,9 +79,28 @@ template <int NO, int THREADS> __device__ __forceinline__ void fill_image(unsign
     }
 }
 
+struct MlpCtxX3 {
+    uint32_t w1f;
+    const float4* w1t;
+    int i, h;
+    uint32_t f2[2], f3[2];  // forward (row-read) lane bases: W2 image halves 0 / 1; W3 image (one half, twice)
+    uint32_t t2[2], t3[2];  // transposed-read lane bases
+};
+
+// the bf16x3 arithmetic as the kernels see it (MlpArith: hjbx_mlp_core.hpp); the members are defined below, where their code has always been
+template <> struct MlpArith<1> {
+    template <int N> using Lds = MlpLdsX3<N>;
+    template <int N, int THREADS>
+    static __device__ void fill(MlpLdsX3<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g, const float* __restrict__ W3g, int tid);
+    template <int N> static __device__ MlpCtxX3 ctx(MlpLdsX3<N>& L, int lane);
+    template <typename S, int TL, int ACT>
+    static __device__ void value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtxX3& c, const float (&xs)[TL][S::N], bool want_grad, float (&V)[TL],
+                                      float (&g)[TL][S::N]);
+};
+
 template <int N, int THREADS>
-__device__ __forceinline__ void mlp_fill_lds_x3(MlpLdsX3<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g,
-                                                const float* __restrict__ W3g, int tid) {
+__device__ __forceinline__ void MlpArith<1>::fill(MlpLdsX3<N>& L, const float* __restrict__ W1g, const float* __restrict__ W2g,
+                                                  const float* __restrict__ W3g, int tid) {
     constexpr int NP = MlpLdsX3<N>::NP;
     for (int idx = tid; idx < N * kH1; idx += THREADS) L.W1[(idx / kH1) * kLD1 + (idx % kH1)] = W1g[idx];
     for (int idx = tid; idx < kH1 * NP; idx += THREADS) {
@@ -97,15 +111,7 @@ __device__ __forceinline__ void mlp_fill_lds_x3(MlpLdsX3<N>& L, const float* __r
     fill_image<kH3, THREADS>(L.W3i, W3g, tid);
 }
 
-struct MlpCtxX3 {
-    uint32_t w1f;
-    const float4* w1t;
-    int i, h;
-    uint32_t f2[2], f3[2];  // forward (row-read) lane bases: W2 image halves 0 / 1; W3 image (one half, twice)
-    uint32_t t2[2], t3[2];  // transposed-read lane bases
-};
-
-template <int N> __device__ __forceinline__ MlpCtxX3 mlp_ctx_x3(MlpLdsX3<N>& L, int lane) {
+template <int N> __device__ __forceinline__ MlpCtxX3 MlpArith<1>::ctx(MlpLdsX3<N>& L, int lane) {
     constexpr int NP = MlpLdsX3<N>::NP;
     MlpCtxX3 c;
     c.i = lane & 31;
@@ -125,20 +131,6 @@ template <int N> __device__ __forceinline__ MlpCtxX3 mlp_ctx_x3(MlpLdsX3<N>& L, 
     c.t2[0] = w2 + trd; c.t2[1] = w2 + kImgHalf + trd;
     c.t3[0] = c.t3[1] = w3 + trd;
     return c;
-}
-
-template <int BYTE_OFF> __device__ __forceinline__ u32x2 lds_read_b64(uint32_t addr) {
-    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 8 == 0, "");
-    u32x2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(BYTE_OFF));
-    return v;
-}
-// EXEC must be all ones (the gather crosses lanes): the chains run with every lane active, padding lanes included
-template <int BYTE_OFF> __device__ __forceinline__ u32x2 lds_read_tr16_b64(uint32_t addr) {
-    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 8 == 0, "");
-    u32x2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(BYTE_OFF));
-    return v;
 }
 
 // One unit of a chain = (k-step K of 16 input features, 32-row output block O): 6 LDS reads (3 pieces x 2) and 6 MFMAs.
@@ -177,24 +169,6 @@ template <typename Dir, int K, int O, int NOUT> __device__ __forceinline__ void 
 }
 
 // pieces of one pair of B-operand elements (2 jj, 2 jj + 1) -> dword jj of the three fragments
-// v = relu(v) and bit BIT of m = [v > 0]
-template <int BIT> __device__ __forceinline__ void relu_mask(float& v, uint32_t& m) {
-    v = relu1(v);
-    uint32_t t;
-    asm("v_min_u32_e32 %0, 1, %2\n\tv_lshl_or_b32 %1, %0, %3, %1" : "=&v"(t), "+v"(m) : "v"(v), "n"(BIT));
-}
-// x * [bit BIT of m]
-template <int BIT> __device__ __forceinline__ float mask_apply(float x, uint32_t m) {
-    float y;
-    asm("v_bfe_i32 %0, %1, %2, 1\n\tv_and_b32_e32 %0, %0, %3" : "=&v"(y) : "v"(m), "n"(BIT), "v"(x));
-    return y;
-}
-
-// What happens to the chain's input registers on their way into the B fragments (PRE): the element-wise work between two products runs
-// inside the consuming chain, two elements per unit next to their split, instead of in a VALU-only pass in front of it (where this
-// wave issues no MFMA for ~500 instructions and relies on its SIMD partner being inside a chain at that moment).
-enum { kPreNone = 0, kPreReluMask = 1, kPreMaskApply = 2 };  // relu + record [v > 0] in the mask | multiply by the recorded mask bit
-
 template <int NIN, int K, int JJ, int PRE> __device__ __forceinline__ void x3_split(const f32x16 (&in)[NIN], uint32_t (&Bp)[3][4], uint32_t (&m)[2]) {
     constexpr int kb = K >> 1, r0 = 8 * (K & 1) + 2 * JJ;  // registers r0, r0 + 1 of block kb: mask bits 16 (kb & 1) + r of m[kb >> 1]
     float x0 = in[kb][r0], x1 = in[kb][r0 + 1];
@@ -265,19 +239,11 @@ __device__ __forceinline__ void x3_chain(f32x16 (&out)[NOUT], const f32x16 (&in)
     mfma_results_barrier<8>();
 }
 
-template <int FB, int R> __device__ __forceinline__ void mask_apply_block(f32x16 (&a)[4], const uint32_t (&m)[2]) {
-    if constexpr (FB < 4) {
-        const float v = a[FB][R];
-        a[FB][R] = mask_apply<16 * (FB & 1) + R>(v, m[FB >> 1]);
-        if constexpr (R + 1 < 16) mask_apply_block<FB, R + 1>(a, m);
-        else mask_apply_block<FB + 1, 0>(a, m);
-    }
-}
-
 // V and dV/dx of one tile of 32 environments (ReLU network); same contract as mlp_value_grad with TL = 1
-template <typename S>
-__device__ __forceinline__ void mlp_value_grad_x3(const S& sys, const MlpP<S::N>& p, const MlpCtxX3& c, const float (&xs)[1][S::N], bool want_grad,
-                                                  float (&V)[1], float (&g)[1][S::N]) {
+template <typename S, int TL, int ACT>
+__device__ __forceinline__ void MlpArith<1>::value_grad(const S& sys, const MlpP<S::N>& p, const MlpCtxX3& c, const float (&xs)[TL][S::N], bool want_grad,
+                                                        float (&V)[TL], float (&g)[TL][S::N]) {
+    static_assert(TL == 1 && ACT == HJBX_ACT_RELU, "bf16x3: one tile per wave, ReLU network");
     constexpr int N = S::N;
     constexpr int NP = MlpLdsX3<N>::NP;
     const int h = c.h;

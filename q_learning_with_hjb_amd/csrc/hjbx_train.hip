@@ -141,7 +141,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_train_chains(S sys_k,
     constexpr int N = S::N, M = S::M, ACT = HJBX_ACT_RELU;
     constexpr int NP = MlpLds<N>::NP;
     static_assert(N % 2 == 0 && N <= 32, "state dimension");
-    __shared__ __attribute__((aligned(256))) std::conditional_t<H2, MlpLdsH2<N>, MlpLds<N>> L;
+    using Arith = MlpArith<H2 ? 2 : 0>;
+    __shared__ __attribute__((aligned(256))) typename Arith::template Lds<N> L;
     __shared__ __attribute__((aligned(16))) unsigned char sys_raw[sizeof(S)];
     S& sys_s = *reinterpret_cast<S*>(sys_raw);
     __shared__ MlpP<N> p_s;
@@ -150,18 +151,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_train_chains(S sys_k,
     __shared__ double red[4][WAVES];
     const int tid = threadIdx.x;
     if (tid == 0) { sys_s = sys_k; p_s = p_k; tk_s = tk_k; lim_s = lim_k; }
-    if constexpr (H2) mlp_fill_lds_h2<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
-    else mlp_fill_lds<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
+    Arith::template fill<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
     __syncthreads();
     const S& sys = sys_s;
     const MlpP<N>& p = p_s;
     const TaskP<float, N, M>& tk = tk_s;
     const Limits<float, M>& lim = lim_s;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // SGPR: tile pointers stay wave uniform (saddr stores)
-    const auto c = [&] {
-        if constexpr (H2) return mlp_ctx_h2<N>(L, lane);
-        else return mlp_ctx<N>(L, lane);
-    }();
+    const auto c = [&] { return Arith::template ctx<N>(L, lane); }();
     const int i = c.i, h = c.h;
     double acc_h = 0, acc_t = 0, acc_ni = 0, acc_nd = 0;
     // the four big products; each returns the exponent its result carries on top of its input's (0 for the f32 chains).  LDS reads run two
@@ -191,14 +188,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_train_chains(S sys_k,
     // behind a tile's ~160 stores could only be waited for by draining them all
     auto fetch = [&](int64_t tile, float (&xv)[N], float& dnv, float& cstv) __attribute__((always_inline)) {
         const int64_t env = tile * 32 + i;
-        const bool ok = tile < ntiles && env < B;
-        if (ok) load_row<N>(x, env, xv);
-        else {
-#pragma unroll
-            for (int k = 0; k < N; ++k) xv[k] = p.xf[k];
-        }
-        dnv = ok ? done[env] : 0.f;
-        cstv = ok ? cost[env] : 1.f;
+        load_sample<N>(x, cost, done, p, env, tile < ntiles && env < B, xv, dnv, cstv);
     };
     float xs_n[N], dn_n, cst_n;
     fetch((int64_t)wave * gridDim.x + blockIdx.x, xs_n, dn_n, cst_n);
@@ -494,10 +484,7 @@ __global__ __launch_bounds__(512, 2) void k_train_outer(const float* __restrict_
     }
     // partial sums of this workgroup, raw accumulator layout [block][register][lane]
     float* out = partial + (int64_t)blockIdx.x * kBlocks * 1024;
-    auto put = [&](int blk, const f32x16& a) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[blk * 1024 + r * 64 + lane] = a[r];
-    };
+    auto put = [&](int blk, const f32x16& a) { put_acc_block(out, blk, lane, a); };
     if (wave < 4) {
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) { put(4 + wave * 4 + jb, acc[jb]); put(kBlocksPerSet + 4 + wave * 4 + jb, acc[4 + jb]); }

@@ -283,14 +283,7 @@ __global__ __launch_bounds__(256, 1) void k_train_coop(S sys_k, MlpP<S::N> p_k, 
     // outer products of one 32-sample tile (coop_outer below): acc[j] += A (x) B_j over the 16 k-steps (2 samples each)
     auto fetch = [&](int64_t tile, float (&xv)[N], float& dnv, float& cstv) __attribute__((always_inline)) {
         const int64_t env = tile * 32 + i;
-        const bool ok = tile < ntiles && env < B;
-        if (ok) load_row<N>(x, env, xv);
-        else {
-#pragma unroll
-            for (int k = 0; k < N; ++k) xv[k] = p.xf[k];
-        }
-        dnv = ok ? done[env] : 0.f;
-        cstv = ok ? cost[env] : 1.f;
+        load_sample<N>(x, cost, done, p, env, tile < ntiles && env < B, xv, dnv, cstv);
     };
     float xs_n[N], dn_n, cst_n;
     const int64_t tile_stride = gridDim.x / (unsigned)psplit;
@@ -629,10 +622,7 @@ __global__ __launch_bounds__(256, 1) void k_train_coop(S sys_k, MlpP<S::N> p_k, 
     COOP_STAMP();                                                                       // tile loop and dW1 tail done
     // ---- partial sums of this workgroup (added in workgroup order by k_train_coop_reduce: deterministic, no float atomics) ------------------
     float* out = partial + (int64_t)blockIdx.x * kCoopBlocks * 1024;
-    auto put = [&](int blk, const f32x16& a) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[blk * 1024 + r * 64 + lane] = a[r];
-    };
+    auto put = [&](int blk, const f32x16& a) { put_acc_block(out, blk, lane, a); };
     if constexpr (PS == 4) {   // only the blocks this part owns are written -- and only those are read: the epilogue kernels know the ownership
         put(w * 4 + part, acc2h[0]);
         put(kCoopSet + w * 4 + part, acc2t[0]);
