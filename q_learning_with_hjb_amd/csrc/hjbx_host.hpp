@@ -3,6 +3,7 @@
 #pragma once
 #include <atomic>
 #include <cstring>
+#include <new>
 #include <type_traits>
 
 #include "hjbx_internal.hpp"
@@ -96,18 +97,68 @@ inline bool aligned_rows(const void* p, size_t row_bytes, uintptr_t least = 3u) 
     return (reinterpret_cast<uintptr_t>(p) & a) == 0;
 }
 
-// Calls f(integral_constant<int, n>, integral_constant<int, m>) for the (even) state and control dimension of a user-defined system whose
-// matrix-core kernels are enabled; `what` names the missing kernel otherwise
-template <typename F> inline int with_mc_dims(const hjbx_system* s, const char* who, const char* what, F&& f) {
-#define HJBX_UD(NN)                                                                                   \
-    case NN:                                                                                          \
-        if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
-        if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
-        if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
+// Calls f(integral_constant<int, n>, integral_constant<int, m>) for the handle's dimensions, n a multiple of STEP, and returns f's status;
+// kNoDims (no status has this value) when the handle has others
+static constexpr int kNoDims = 1;
+template <int STEP, typename F> inline int with_dims(const hjbx_system* s, F&& f) {
+#define HJBX_UD(NN)                                                                                       \
+    case NN:                                                                                              \
+        if constexpr (NN % STEP == 0) {                                                                   \
+            if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
+            if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
+            if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
+        }                                                                                                 \
         break;
-    switch (s->n) { HJBX_UD(2) HJBX_UD(4) HJBX_UD(6) HJBX_UD(8) HJBX_UD(10) }
+    switch (s->n) { HJBX_UD(1) HJBX_UD(2) HJBX_UD(3) HJBX_UD(4) HJBX_UD(5) HJBX_UD(6) HJBX_UD(7) HJBX_UD(8) HJBX_UD(9) HJBX_UD(10) }
 #undef HJBX_UD
-    return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no %s for a user system with n=%d m=%d", who, what, s->n, s->m);
+    return kNoDims;
+}
+// ... for the (even) state dimension of a user-defined system whose matrix-core kernels are enabled; `what` names the missing kernel otherwise
+template <typename F> inline int with_mc_dims(const hjbx_system* s, const char* who, const char* what, F&& f) {
+    const int rc = with_dims<2>(s, f);
+    return rc == kNoDims ? hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no %s for a user system with n=%d m=%d", who, what, s->n, s->m) : rc;
+}
+
+// A user-defined system (HJBX_SYS_USER) on the host.  The first argument of every run-time compiled kernel is `struct { T p[n_params]; }`:
+// UserBlob; UserRef stands for the handle where a built-in system has its device POD: it carries N and M for the argument structs, and no
+// kernel of the library is ever instantiated for it.
+template <typename T> struct UserBlob { T p[HJBX_USER_MAX_PARAMS]; };
+template <typename T> inline UserBlob<T> user_blob(const hjbx_system* s) {
+    UserBlob<T> b;
+    for (int i = 0; i < HJBX_USER_MAX_PARAMS; ++i) b.p[i] = i < s->n_params ? (T)s->p[i] : T(0);
+    return b;
+}
+template <typename T, int N_, int M_> struct UserRef {
+    static constexpr int N = N_, M = M_;
+    static constexpr bool kHasZoh = false;
+    const hjbx_system* handle;
+    UserBlob<T> blob;
+};
+template <typename S> struct is_user { static constexpr bool value = false; };
+template <typename T, int N, int M> struct is_user<UserRef<T, N, M>> { static constexpr bool value = true; };
+
+// Calls f(S) and returns its status: S = the device system POD of a built-in handle (with_system), or the UserRef of a user-defined one
+template <typename T, typename F> inline int with_any_system(const hjbx_system* s, F&& f) {
+    if (s->kind == HJBX_SYS_USER) {
+        const int rc = with_dims<1>(s, [&](auto Nc, auto Mc) -> int { return f(UserRef<T, decltype(Nc)::value, decltype(Mc)::value>{s, user_blob<T>(s)}); });
+        return rc == kNoDims ? hjbx_set_error(HJBX_EUNSUPPORTED, "user system with n=%d m=%d", s->n, s->m) : rc;
+    }
+    int rc = HJBX_OK;
+    if (!with_system<T>(s, [&](auto S) { rc = f(S); }))
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "no kernel for system kind %d with n=%d m=%d", s->kind, s->n, s->m);
+    return rc;
+}
+
+// A new handle with every field filled (`user`: the run-time compiled program of a HJBX_SYS_USER handle); NULL when the host is out of memory
+inline hjbx_system* new_system(int kind, int n, int m, double dt, const double* umin, const double* umax, const double* params, int n_params,
+                               void* user) {
+    hjbx_system* s = new (std::nothrow) hjbx_system();
+    if (!s) return nullptr;
+    memset(s, 0, sizeof(*s));
+    s->kind = kind; s->n = n; s->m = m; s->dt = dt; s->n_params = n_params; s->user = user;
+    for (int j = 0; j < m; ++j) { s->umin[j] = umin[j]; s->umax[j] = umax[j]; }
+    for (int i = 0; i < n_params; ++i) s->p[i] = params[i];
+    return s;
 }
 
 // Compute units of the CURRENT device (sizes the persistent grids and their workspaces); cached per device ordinal, not per process:

@@ -50,8 +50,8 @@ int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_ne
 // the handle's train unit for `activation` (hjbx_user_train_kernels.hpp: k_train_coop<0|1, activation, 1|4, UserSystem<float>>), compiled now
 // if this is the first request; HJBX_EUNSUPPORTED when the handle is not enabled or one of the four kernels needs scratch (the whole unit is
 // refused and the refusal remembered), HJBX_EINVAL when the source does not compile there.  hjbx_user_train_launch: enqueue the kernel for
-// (mode 0 | 1, psplit 1 | 4) with `grid` workgroups of 256 threads; args = pointers to the kernel's arguments in order, args[0] (the system
-// struct) is filled in by the callee.
+// (mode 0 | 1, psplit 1 | 4) with `grid` workgroups of 256 threads; args = pointers to the kernel's arguments in order (args[0] points at the
+// system blob, as for hjbx_user_launch).
 int hjbx_user_train_unit(const hjbx_system* s, int activation, const char* who);
 int hjbx_user_train_launch(const hjbx_system* s, int activation, int mode, int psplit, unsigned grid, void** args, void* stream, const char* who);
 

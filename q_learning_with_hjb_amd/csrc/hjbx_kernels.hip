@@ -174,45 +174,77 @@ __global__ __launch_bounds__(kBlock) void k_rollout_feedback(S sys, TaskP<T, S::
 }
 
 // ----------------------------------------------------------------------------------------------
-// user-defined systems (HJBX_SYS_USER, hjbx_system_create_from_source): the same kernel bodies, compiled at run time for the user's struct
-// (hjbx_user.hip / hjbx_user_kernels.hpp).  Here: the typed kernel arguments for the handle's (n, m) and the launch by name.
+// One launch path for the built-in systems and the user-defined ones (HJBX_SYS_USER, hjbx_system_create_from_source: the same kernel bodies,
+// compiled at run time for the user's struct -- hjbx_user.hip / hjbx_user_kernels.hpp -- and launched by name).
+// A tag per entry point names the built-in template k_<base><V..., S, T> and its run-time compiled twin hjbx_u_<base>[_<c><V0>]_<f32|f64>:
+// the integrator / residual mode is in the name (c = 'i' / 'm'), and a user code object holds the variants with every other V == rest only
+// (one row per thread, controller kind 0).
 // ----------------------------------------------------------------------------------------------
-template <typename T> struct UserBlob { T p[HJBX_USER_MAX_PARAMS]; };   // the kernel's first argument is `struct { T p[n_params]; }`
-template <typename T> static UserBlob<T> user_blob(const hjbx_system* s) {
-    UserBlob<T> b;
-    for (int i = 0; i < HJBX_USER_MAX_PARAMS; ++i) b.p[i] = i < s->n_params ? (T)s->p[i] : T(0);
-    return b;
+#define HJBX_KERNEL(tag, base_, c_, rest_)                                                                                          \
+    template <int... V> struct tag {                                                                                                \
+        template <typename S, typename T> using sig = decltype(&k_##base_<V..., S, T>);   /* unevaluated: instantiates no kernel */ \
+        template <typename S, typename T> static const void* fn() { return reinterpret_cast<const void*>(&k_##base_<V..., S, T>); } \
+        static constexpr const char* base = #base_;                                                                                 \
+        static constexpr char c = c_;                                                                                               \
+        static constexpr int rest = rest_, nv = sizeof...(V), v[sizeof...(V) + 1] = {V..., 0};                                      \
+    };
+HJBX_KERNEL(KAffine, affine, 0, 0) HJBX_KERNEL(KWrap, wrap, 0, 0) HJBX_KERNEL(KXdot, xdot, 0, 0) HJBX_KERNEL(KSimulate, simulate, 'i', 1)
+HJBX_KERNEL(KInitialState, initial_state, 0, 0) HJBX_KERNEL(KInitialStatePhilox, initial_state_philox, 0, -1)
+HJBX_KERNEL(KRunningCost, running_cost, 0, 0) HJBX_KERNEL(KTerminationCost, termination_cost, 0, 0)
+HJBX_KERNEL(KControlFromGrad, control_from_grad, 0, 0) HJBX_KERNEL(KController, controller, 0, 0) HJBX_KERNEL(KHjbResidual, hjb_residual, 'm', 1)
+HJBX_KERNEL(KVhjbStep, vhjb_step, 'i', 1) HJBX_KERNEL(KRolloutFeedback, rollout_feedback, 'i', 0)
+#undef HJBX_KERNEL
+template <typename K> static constexpr bool user_variant_exists() {
+    for (int i = K::c ? 1 : 0; i < K::nv; ++i)
+        if (K::v[i] != K::rest) return false;
+    return K::rest >= 0;
 }
-template <int N_> struct DimsOnly { static constexpr int N = N_; };      // X0P<S, T> depends on S::N only
-template <typename T> struct UName {
-    char buf[64];
-    explicit UName(const char* base) { snprintf(buf, sizeof buf, "hjbx_u_%s_%s", base, sizeof(T) == 4 ? "f32" : "f64"); }
-    operator const char*() const { return buf; }
-};
-// calls f(integral_constant<int, n>, integral_constant<int, m>) for the handle's dimensions
-template <typename F> static int with_user_dims(const hjbx_system* s, F&& f) {
-#define HJBX_UD(NN)                                                              \
-    case NN:                                                                     \
-        if (s->m == 1) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 1>{}); \
-        if (s->m == 2) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 2>{}); \
-        if (s->m == 3) return f(std::integral_constant<int, NN>{}, std::integral_constant<int, 3>{}); \
-        break;
-    switch (s->n) { HJBX_UD(1) HJBX_UD(2) HJBX_UD(3) HJBX_UD(4) HJBX_UD(5) HJBX_UD(6) HJBX_UD(7) HJBX_UD(8) HJBX_UD(9) HJBX_UD(10) }
-#undef HJBX_UD
-    return hjbx_set_error(HJBX_EUNSUPPORTED, "user system with n=%d m=%d", s->n, s->m);
+
+// Enqueue kernel K for S: `grid` workgroups of kBlock threads on `st`, kernel arguments (S, args...).  The pack must have EXACTLY the kernel's
+// parameter types (no bool or narrower integer that a call would convert): both arms pass the addresses of these very objects.
+template <typename T, typename K, typename S, typename... A>
+static int launch(K, const S& sys, dim3 grid, void* st, const char* who, const A&... args) {
+    static_assert(std::is_same<typename K::template sig<S, T>, void (*)(S, A...)>::value, "launch: the arguments are not the kernel's parameter types");
+    if constexpr (is_user<S>::value) {
+        static_assert(user_variant_exists<K>(), "launch: a user code object has no such kernel");
+        char name[64];
+        if (K::c) snprintf(name, sizeof name, "hjbx_u_%s_%c%d_%s", K::base, K::c, K::v[0], sizeof(T) == 4 ? "f32" : "f64");
+        else snprintf(name, sizeof name, "hjbx_u_%s_%s", K::base, sizeof(T) == 4 ? "f32" : "f64");
+        void* a[] = {(void*)&sys.blob, (void*)&args...};
+        return hjbx_user_launch(sys.handle, name, grid.x, a, st);
+    } else {
+        void* a[] = {(void*)&sys, (void*)&args...};
+        (void)hipLaunchKernel(K::template fn<S, T>(), grid, dim3(kBlock), a, 0, (hipStream_t)st);
+        return check_launch(who);
+    }
 }
-#define HJBX_USER(sys, ...) \
-    if ((sys)->kind == HJBX_SYS_USER) return with_user_dims(sys, [&](auto Nc, auto Mc) -> int { \
-        constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value; (void)N; (void)M;      \
-        auto blob = user_blob<T>(sys);                                                         \
-        __VA_ARGS__                                                                            \
-    })
-static unsigned ugrid(int64_t B) { return (unsigned)((B + kBlock - 1) / kBlock); }
 
-// host side: descriptor conversion and dispatch live in hjbx_host.hpp (shared with hjbx_mlp.hip)
-
-static int unsupported(const hjbx_system* s) {
-    return hjbx_set_error(HJBX_EUNSUPPORTED, "no kernel for system kind %d with n=%d m=%d", s->kind, s->n, s->m);
+// run-time choice -> integral_constant, each calls f(constant) and returns its status.  Rows per thread (a user code object: one):
+template <typename T, typename S, typename F> static int with_rows(int64_t B, bool reducing, F&& f) {
+    if constexpr (!is_user<S>::value) {
+        const int R = rows_per_thread<T>(B, S::N, reducing);
+        if (R == 4) return f(std::integral_constant<int, 4>{});
+        if (R == 2) return f(std::integral_constant<int, 2>{});
+    }
+    return f(std::integral_constant<int, 1>{});
+}
+// ... the integrator (checked by check_integrator: HJBX_ZOH reaches a LINEAR system only)
+template <typename S, typename F> static int with_integrator(int integ, F&& f) {
+    if (integ == HJBX_EULER) return f(std::integral_constant<int, 0>{});
+    if (integ == HJBX_RK4) return f(std::integral_constant<int, 1>{});
+    if constexpr (is_linear<S>::value) return f(std::integral_constant<int, 2>{});
+    return HJBX_OK;
+}
+// ... the controller kind (checked by check_ctrl): the three special controllers exist for their own system type, 0 = linear feedback
+template <typename S> struct is_cartpole { static constexpr bool value = false; };
+template <typename T> struct is_cartpole<Cartpole<T>> { static constexpr bool value = true; };
+template <typename S> struct is_acrobot { static constexpr bool value = false; };
+template <typename T> struct is_acrobot<Acrobot<T>> { static constexpr bool value = true; };
+template <typename S, typename F> static int with_ctrl_kind(const hjbx_controller* c, F&& f) {
+    if constexpr (is_cartpole<S>::value) if (c->kind == HJBX_CTRL_CARTPOLE_ENERGY) return f(std::integral_constant<int, 1>{});
+    if constexpr (is_di<S>::value) if (c->kind == HJBX_CTRL_DI_TIME_OPTIMAL) return f(std::integral_constant<int, 3>{});
+    if constexpr (is_acrobot<S>::value) if (c->kind == HJBX_CTRL_ACROBOT_ENERGY) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -228,58 +260,40 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 #define HJBX_CHECK_OPT(p, cols) \
     HJBX_REQUIRE((p) == nullptr || aligned_rows(p, (size_t)(cols) * sizeof(T)), #p " must be aligned to its row vector width")
 
-// ---- typed implementations ---------------------------------------------------------------------
+// ---- typed implementations: the argument checks, then the kernel's arguments built once and handed to launch() ------------------------
 template <typename T> static int affine_impl(const hjbx_system* sys, const T* x, T* f1, T* f2, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(f1, sys->n); HJBX_CHECK_ROWS(f2, sys->n * sys->m);
-    HJBX_USER(sys, void* a[] = {&blob, (void*)&x, (void*)&f1, (void*)&f2, (void*)&B}; return hjbx_user_launch(sys, UName<T>("affine"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            hipLaunchKernelGGL((k_affine<decltype(S), T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, x, f1, f2, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_affine");
+    return with_any_system<T>(sys, [&](auto S) { return launch<T>(KAffine<>{}, S, grid_for(B), st, "hjbx_affine", x, f1, f2, B); });
 }
 
 template <typename T> static int wrap_impl(const hjbx_system* sys, const T* x, T* out, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(out, sys->n);
-    HJBX_USER(sys, void* a[] = {&blob, (void*)&x, (void*)&out, (void*)&B}; return hjbx_user_launch(sys, UName<T>("wrap"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            hipLaunchKernelGGL((k_wrap<decltype(S), T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, x, out, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_wrap");
+    return with_any_system<T>(sys, [&](auto S) { return launch<T>(KWrap<>{}, S, grid_for(B), st, "hjbx_wrap", x, out, B); });
 }
 
 template <typename T> static int xdot_impl(const hjbx_system* sys, const T* x, const T* u, T* xd, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(u, sys->m); HJBX_CHECK_ROWS(xd, sys->n);
-    HJBX_USER(sys, void* a[] = {&blob, (void*)&x, (void*)&u, (void*)&xd, (void*)&B}; return hjbx_user_launch(sys, UName<T>("xdot"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            hipLaunchKernelGGL((k_xdot<decltype(S), T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, x, u, xd, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_dynamics_step");
+    return with_any_system<T>(sys, [&](auto S) { return launch<T>(KXdot<>{}, S, grid_for(B), st, "hjbx_dynamics_step", x, u, xd, B); });
 }
 
 template <typename T>
 static int simulate_impl(const hjbx_system* sys, int integ, const T* x, const T* u, T* xn, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(u, sys->m); HJBX_CHECK_ROWS(xn, sys->n);
     if (int rc = check_integrator(sys, integ, "hjbx_simulate")) return rc;
-    HJBX_USER(sys, auto lim = make_limits<T, M>(sys); void* a[] = {&blob, &lim, (void*)&x, (void*)&u, (void*)&xn, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>(integ == HJBX_RK4 ? "simulate_i1" : "simulate_i0"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            auto lim = make_limits<T, SS::M>(sys);
-            auto go = [&](auto integc, auto rc) {
-                constexpr int I = decltype(integc)::value, R = decltype(rc)::value;
-                hipLaunchKernelGGL((k_simulate<I, R, SS, T>), grid_rows(B, R), dim3(kBlock), 0, (hipStream_t)st, S, lim, x, u, xn, B);
-            };
-            auto with_r = [&](auto integc) {
-                const int R = rows_per_thread<T>(B, SS::N);
-                if (R == 4) go(integc, std::integral_constant<int, 4>{});
-                else if (R == 2) go(integc, std::integral_constant<int, 2>{});
-                else go(integc, std::integral_constant<int, 1>{});
-            };
-            if (integ == HJBX_EULER) with_r(std::integral_constant<int, 0>{});
-            else if (integ == HJBX_RK4) with_r(std::integral_constant<int, 1>{});
-            else if constexpr (is_linear<SS>::value) with_r(std::integral_constant<int, 2>{});
-        })) return unsupported(sys);
-    return check_launch("hjbx_simulate");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto lim = make_limits<T, SS::M>(sys);
+        return with_integrator<SS>(integ, [&](auto ic) { return with_rows<T, SS>(B, false, [&](auto rc) {
+            constexpr int I = decltype(ic)::value, R = decltype(rc)::value;
+            return launch<T>(KSimulate<I, R>{}, S, grid_rows(B, R), st, "hjbx_simulate", lim, x, u, xn, B);
+        }); });
+    });
+}
+
+template <typename SS, typename T> static X0P<SS, T> make_x0(const double* mean, const double* sd) {
+    X0P<SS, T> p;
+    for (int i = 0; i < SS::N; ++i) { p.mean[i] = (T)mean[i]; p.std[i] = (T)sd[i]; }
+    return p;
 }
 
 template <typename T>
@@ -287,15 +301,9 @@ static int initial_state_impl(const hjbx_system* sys, const double* mean, const 
                               void* st) {
     HJBX_CHECK_COMMON(sys, B); HJBX_CHECK_ROWS(u01, sys->n); HJBX_CHECK_ROWS(x0, sys->n);
     HJBX_REQUIRE(mean && sd, "x0_mean / x0_std are NULL");
-    HJBX_USER(sys, X0P<DimsOnly<N>, T> p; for (int i = 0; i < N; ++i) { p.mean[i] = (T)mean[i]; p.std[i] = (T)sd[i]; }
-              void* a[] = {&blob, &p, (void*)&u01, (void*)&x0, (void*)&B}; return hjbx_user_launch(sys, UName<T>("initial_state"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            X0P<SS, T> p;
-            for (int i = 0; i < SS::N; ++i) { p.mean[i] = (T)mean[i]; p.std[i] = (T)sd[i]; }
-            hipLaunchKernelGGL((k_initial_state<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, p, u01, x0, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_initial_state");
+    return with_any_system<T>(sys, [&](auto S) {
+        return launch<T>(KInitialState<>{}, S, grid_for(B), st, "hjbx_initial_state", make_x0<decltype(S), T>(mean, sd), u01, x0, B);
+    });
 }
 
 // a (B, n) temporary in stream order: taken from and returned to the runtime's pool without stopping the host (the blocking pair is the
@@ -322,65 +330,53 @@ static int initial_state_philox_impl(const hjbx_system* sys, const double* mean,
     HJBX_REQUIRE(x0 != nullptr || B == 0, "x0 is NULL");
     if (B == 0) return HJBX_OK;
     HJBX_CHECK_ROWS(x0, sys->n);
-    if (sys->kind == HJBX_SYS_USER) {
-        // two kernels: the library's uniforms into a temporary, then the handle's own hjbx_u_initial_state_* (the same body as the fused kernel)
-        void* tmp = nullptr;
-        bool pooled = false;
-        hipError_t e = temp_alloc(&tmp, (size_t)B * sys->n * sizeof(T), (hipStream_t)st, &pooled);
-        if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hjbx_initial_state_philox: %s", hipGetErrorString(e));
-        T* u01 = (T*)tmp;
-        hipLaunchKernelGGL((k_philox_uniforms<T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, seed, first_row, sys->n, u01, B);
-        int rc = check_launch("hjbx_initial_state_philox");
-        if (rc == HJBX_OK) rc = initial_state_impl<T>(sys, mean, sd, u01, x0, B, st);
-        temp_free(tmp, (hipStream_t)st, pooled);
-        return rc;
-    }
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            X0P<SS, T> p;
-            for (int i = 0; i < SS::N; ++i) { p.mean[i] = (T)mean[i]; p.std[i] = (T)sd[i]; }
-            hipLaunchKernelGGL((k_initial_state_philox<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, p, seed, first_row, x0, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_initial_state_philox");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto p = make_x0<SS, T>(mean, sd);
+        if constexpr (is_user<SS>::value) {
+            // two kernels: the library's uniforms into a temporary, then the handle's own hjbx_u_initial_state_* (the same body as the fused kernel)
+            void* tmp = nullptr;
+            bool pooled = false;
+            hipError_t e = temp_alloc(&tmp, (size_t)B * sys->n * sizeof(T), (hipStream_t)st, &pooled);
+            if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "hjbx_initial_state_philox: %s", hipGetErrorString(e));
+            const T* u01 = (const T*)tmp;
+            hipLaunchKernelGGL((k_philox_uniforms<T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, seed, first_row, sys->n, (T*)tmp, B);
+            int rc = check_launch("hjbx_initial_state_philox");
+            if (rc == HJBX_OK) rc = launch<T>(KInitialState<>{}, S, grid_for(B), st, "hjbx_initial_state", p, u01, x0, B);
+            temp_free(tmp, (hipStream_t)st, pooled);
+            return rc;
+        } else {
+            return launch<T>(KInitialStatePhilox<>{}, S, grid_for(B), st, "hjbx_initial_state_philox", p, seed, first_row, x0, B);
+        }
+    });
 }
 
 template <typename T>
 static int running_cost_impl(const hjbx_system* sys, const hjbx_task* task, const T* x, const T* u, T* cost, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); if (int rc = check_task(task)) return rc; HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(u, sys->m); HJBX_CHECK_ROWS(cost, 1);
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); void* a[] = {&blob, &tk, (void*)&x, (void*)&u, (void*)&cost, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>("running_cost"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            hipLaunchKernelGGL((k_running_cost<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S,
-                               make_task<T, SS::N, SS::M>(task), x, u, cost, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_running_cost");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        return launch<T>(KRunningCost<>{}, S, grid_for(B), st, "hjbx_running_cost", make_task<T, SS::N, SS::M>(task), x, u, cost, B);
+    });
 }
 
 template <typename T>
 static int termination_cost_impl(const hjbx_system* sys, const hjbx_task* task, const T* x, T* cost, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); if (int rc = check_task(task)) return rc; HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(cost, 1);
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); void* a[] = {&blob, &tk, (void*)&x, (void*)&cost, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>("termination_cost"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            hipLaunchKernelGGL((k_termination_cost<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S,
-                               make_task<T, SS::N, SS::M>(task), x, cost, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_termination_cost");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        return launch<T>(KTerminationCost<>{}, S, grid_for(B), st, "hjbx_termination_cost", make_task<T, SS::N, SS::M>(task), x, cost, B);
+    });
 }
 
 template <typename T>
 static int control_from_grad_impl(const hjbx_system* sys, const hjbx_task* task, const T* x, const T* g, T* u, int64_t B, void* st) {
     HJBX_CHECK_COMMON(sys, B); if (int rc = check_task(task)) return rc; HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(g, sys->n); HJBX_CHECK_ROWS(u, sys->m);
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); auto lim = make_limits<T, M>(sys);
-              void* a[] = {&blob, &tk, &lim, (void*)&x, (void*)&g, (void*)&u, (void*)&B}; return hjbx_user_launch(sys, UName<T>("control_from_grad"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            hipLaunchKernelGGL((k_control_from_grad<SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S,
-                               make_task<T, SS::N, SS::M>(task), make_limits<T, SS::M>(sys), x, g, u, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_control_from_grad");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        return launch<T>(KControlFromGrad<>{}, S, grid_for(B), st, "hjbx_control_from_grad", make_task<T, SS::N, SS::M>(task), make_limits<T, SS::M>(sys),
+                         x, g, u, B);
+    });
 }
 
 static inline int reduce_grid(int64_t B) {
@@ -404,30 +400,18 @@ static int hjb_residual_impl(const hjbx_system* sys, const hjbx_task* task, int 
         return HJBX_OK;
     }
     HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(g, sys->n); HJBX_CHECK_ROWS(done, 1); HJBX_CHECK_OPT(loss_i, 1); HJBX_CHECK_OPT(dl_dg, sys->n);
-    const int grid = reduce_grid(B);
+    const dim3 grid(reduce_grid(B));
     unsigned char* ws = sums ? (unsigned char*)workspace : nullptr;
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); auto lim = make_limits<T, M>(sys);
-              void* a[] = {&blob, &tk, &lim, (void*)&x, (void*)&g, (void*)&done, (void*)&loss_i, (void*)&dl_dg, (void*)&ws, (void*)&sums, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>(mode == HJBX_RESIDUAL_RAW ? "hjb_residual_m1" : "hjb_residual_m0"), (unsigned)grid, a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            auto tk = make_task<T, SS::N, SS::M>(task);
-            auto lim = make_limits<T, SS::M>(sys);
-            auto go = [&](auto modec, auto rc) {
-                constexpr int MD = decltype(modec)::value, R = decltype(rc)::value;
-                hipLaunchKernelGGL((k_hjb_residual<MD, R, SS, T>), dim3(grid), dim3(kBlock), 0, (hipStream_t)st, S, tk, lim, x, g, done, loss_i, dl_dg,
-                                   ws, sums, B);
-            };
-            auto with_r = [&](auto modec) {
-                const int R = rows_per_thread<T>(B, SS::N, true);
-                if (R == 4) go(modec, std::integral_constant<int, 4>{});
-                else if (R == 2) go(modec, std::integral_constant<int, 2>{});
-                else go(modec, std::integral_constant<int, 1>{});
-            };
-            if (mode == HJBX_RESIDUAL_NORMALISED) with_r(std::integral_constant<int, 0>{});
-            else with_r(std::integral_constant<int, 1>{});
-        })) return unsupported(sys);
-    return check_launch("hjbx_hjb_residual");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto tk = make_task<T, SS::N, SS::M>(task);
+        const auto lim = make_limits<T, SS::M>(sys);
+        auto go = [&](auto mc) { return with_rows<T, SS>(B, true, [&](auto rc) {
+            return launch<T>(KHjbResidual<decltype(mc)::value, decltype(rc)::value>{}, S, grid, st, "hjbx_hjb_residual", tk, lim, x, g, done, loss_i, dl_dg,
+                             ws, sums, B);
+        }); };
+        return mode == HJBX_RESIDUAL_NORMALISED ? go(std::integral_constant<int, 0>{}) : go(std::integral_constant<int, 1>{});
+    });
 }
 
 template <typename T>
@@ -458,36 +442,17 @@ static int vhjb_step_impl(const hjbx_system* sys, const hjbx_task* task, int int
     HJBX_REQUIRE(t >= 0 && T_max >= 0, "negative step index");
     HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(g, sys->n); HJBX_CHECK_ROWS(xn, sys->n); HJBX_CHECK_OPT(u_out, sys->m);
     HJBX_REQUIRE(cost_t && done_t && done_step, "cost_t/done_t/done_step must be non-NULL");
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); auto lim = make_limits<T, M>(sys);
-              void* a[] = {&blob, &tk, &lim, (void*)&t, (void*)&T_max, (void*)&x, (void*)&g, (void*)&xn, (void*)&u_out, (void*)&cost_t, (void*)&done_t,
-                           (void*)&done_step, (void*)&resid_t, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>(integ == HJBX_RK4 ? "vhjb_step_i1" : "vhjb_step_i0"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            auto tk = make_task<T, SS::N, SS::M>(task);
-            auto lim = make_limits<T, SS::M>(sys);
-            auto go = [&](auto integc, auto rc) {
-                constexpr int I = decltype(integc)::value, R = decltype(rc)::value;
-                hipLaunchKernelGGL((k_vhjb_step<I, R, SS, T>), grid_rows(B, R), dim3(kBlock), 0, (hipStream_t)st, S, tk, lim, t, T_max, x,
-                                   g, xn, u_out, cost_t, done_t, done_step, resid_t, B);
-            };
-            auto with_r = [&](auto integc) {
-                const int R = rows_per_thread<T>(B, SS::N);
-                if (R == 4) go(integc, std::integral_constant<int, 4>{});
-                else if (R == 2) go(integc, std::integral_constant<int, 2>{});
-                else go(integc, std::integral_constant<int, 1>{});
-            };
-            if (integ == HJBX_EULER) with_r(std::integral_constant<int, 0>{});
-            else if (integ == HJBX_RK4) with_r(std::integral_constant<int, 1>{});
-            else if constexpr (is_linear<SS>::value) with_r(std::integral_constant<int, 2>{});
-        })) return unsupported(sys);
-    return check_launch("hjbx_vhjb_step");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto tk = make_task<T, SS::N, SS::M>(task);
+        const auto lim = make_limits<T, SS::M>(sys);
+        return with_integrator<SS>(integ, [&](auto ic) { return with_rows<T, SS>(B, false, [&](auto rc) {
+            constexpr int I = decltype(ic)::value, R = decltype(rc)::value;
+            return launch<T>(KVhjbStep<I, R>{}, S, grid_rows(B, R), st, "hjbx_vhjb_step", tk, lim, t, T_max, x, g, xn, u_out, cost_t, done_t, done_step,
+                             resid_t, B);
+        }); });
+    });
 }
-
-template <typename S> struct is_cartpole { static constexpr bool value = false; };
-template <typename T> struct is_cartpole<Cartpole<T>> { static constexpr bool value = true; };
-template <typename S> struct is_acrobot { static constexpr bool value = false; };
-template <typename T> struct is_acrobot<Acrobot<T>> { static constexpr bool value = true; };
 
 static int check_ctrl(const hjbx_system* sys, const hjbx_controller* c) {
     HJBX_REQUIRE(c, "controller is NULL");
@@ -508,57 +473,12 @@ static int controller_impl(const hjbx_system* sys, const hjbx_controller* c, con
     HJBX_CHECK_COMMON(sys, B);
     if (int rc = check_ctrl(sys, c)) return rc;
     HJBX_CHECK_ROWS(x, sys->n); HJBX_CHECK_ROWS(u, sys->m);
-    HJBX_USER(sys, auto cp = make_ctrl<T, N, M>(c); auto lim = make_limits<T, M>(sys);
-              void* a[] = {&blob, &cp, &lim, (void*)&x, (void*)&u, (void*)&B}; return hjbx_user_launch(sys, UName<T>("controller"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            auto cp = make_ctrl<T, SS::N, SS::M>(c);
-            auto lim = make_limits<T, SS::M>(sys);
-            if constexpr (is_cartpole<SS>::value) {
-                if (c->kind == HJBX_CTRL_CARTPOLE_ENERGY) {
-                    hipLaunchKernelGGL((k_controller<1, SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, cp, lim, x, u, B);
-                    return;
-                }
-            }
-            if constexpr (is_di<SS>::value) {
-                if (c->kind == HJBX_CTRL_DI_TIME_OPTIMAL) {
-                    hipLaunchKernelGGL((k_controller<3, SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, cp, lim, x, u, B);
-                    return;
-                }
-            }
-            if constexpr (is_acrobot<SS>::value) {
-                if (c->kind == HJBX_CTRL_ACROBOT_ENERGY) {
-                    hipLaunchKernelGGL((k_controller<2, SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, cp, lim, x, u, B);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL((k_controller<0, SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, cp, lim, x, u, B);
-        })) return unsupported(sys);
-    return check_launch("hjbx_controller");
-}
-
-template <int INTEG, typename SS, typename T>
-static void launch_rollout(const hjbx_system* sys, SS S, const hjbx_task* task, const hjbx_controller* c, uint32_t flags,
-                           int T_steps, const T* x0, T* traj, T* u_log, T* cost, int32_t* done_step, T* total_cost, T* x_final,
-                           int64_t B, void* st) {
-    auto tk = make_task<T, SS::N, SS::M>(task);
-    auto cp = make_ctrl<T, SS::N, SS::M>(c);
-    auto lim = make_limits<T, SS::M>(sys);
-    const int has_task = task != nullptr;
-#define HJBX_LAUNCH_RO(CK)                                                                                                    \
-    hipLaunchKernelGGL((k_rollout_feedback<INTEG, CK, SS, T>), grid_for(B), dim3(kBlock), 0, (hipStream_t)st, S, tk, cp, lim, \
-                       flags, has_task, T_steps, x0, traj, u_log, cost, done_step, total_cost, x_final, B)
-    if constexpr (is_cartpole<SS>::value) {
-        if (c->kind == HJBX_CTRL_CARTPOLE_ENERGY) { HJBX_LAUNCH_RO(1); return; }
-    }
-    if constexpr (is_di<SS>::value) {
-        if (c->kind == HJBX_CTRL_DI_TIME_OPTIMAL) { HJBX_LAUNCH_RO(3); return; }
-    }
-    if constexpr (is_acrobot<SS>::value) {
-        if (c->kind == HJBX_CTRL_ACROBOT_ENERGY) { HJBX_LAUNCH_RO(2); return; }
-    }
-    HJBX_LAUNCH_RO(0);
-#undef HJBX_LAUNCH_RO
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto cp = make_ctrl<T, SS::N, SS::M>(c);
+        const auto lim = make_limits<T, SS::M>(sys);
+        return with_ctrl_kind<SS>(c, [&](auto ck) { return launch<T>(KController<decltype(ck)::value>{}, S, grid_for(B), st, "hjbx_controller", cp, lim, x, u, B); });
+    });
 }
 
 template <typename T>
@@ -574,21 +494,17 @@ static int rollout_feedback_impl(const hjbx_system* sys, const hjbx_task* task, 
     if (task) { if (int rc = check_task(task)) return rc; }
     HJBX_REQUIRE(task || (!cost && !total_cost), "cost outputs need a task");
     HJBX_CHECK_ROWS(x0, sys->n); HJBX_CHECK_OPT(traj, sys->n); HJBX_CHECK_OPT(u_log, sys->m); HJBX_CHECK_OPT(x_final, sys->n);
-    HJBX_USER(sys, auto tk = make_task<T, N, M>(task); auto cp = make_ctrl<T, N, M>(c); auto lim = make_limits<T, M>(sys);
-              int has_task = task != nullptr;
-              void* a[] = {&blob, &tk, &cp, &lim, (void*)&flags, &has_task, (void*)&T_steps, (void*)&x0, (void*)&traj, (void*)&u_log, (void*)&cost,
-                           (void*)&done_step, (void*)&total_cost, (void*)&x_final, (void*)&B};
-              return hjbx_user_launch(sys, UName<T>(integ == HJBX_RK4 ? "rollout_feedback_i1" : "rollout_feedback_i0"), ugrid(B), a, st););
-    if (!with_system<T>(sys, [&](auto S) {
-            using SS = decltype(S);
-            if (integ == HJBX_EULER)
-                launch_rollout<0, SS, T>(sys, S, task, c, flags, T_steps, x0, traj, u_log, cost, done_step, total_cost, x_final, B, st);
-            else if (integ == HJBX_RK4)
-                launch_rollout<1, SS, T>(sys, S, task, c, flags, T_steps, x0, traj, u_log, cost, done_step, total_cost, x_final, B, st);
-            else if constexpr (is_linear<SS>::value)
-                launch_rollout<2, SS, T>(sys, S, task, c, flags, T_steps, x0, traj, u_log, cost, done_step, total_cost, x_final, B, st);
-        })) return unsupported(sys);
-    return check_launch("hjbx_rollout_feedback");
+    return with_any_system<T>(sys, [&](auto S) {
+        using SS = decltype(S);
+        const auto tk = make_task<T, SS::N, SS::M>(task);
+        const auto cp = make_ctrl<T, SS::N, SS::M>(c);
+        const auto lim = make_limits<T, SS::M>(sys);
+        const int has_task = task != nullptr;
+        return with_integrator<SS>(integ, [&](auto ic) { return with_ctrl_kind<SS>(c, [&](auto ck) {
+            return launch<T>(KRolloutFeedback<decltype(ic)::value, decltype(ck)::value>{}, S, grid_for(B), st, "hjbx_rollout_feedback", tk, cp, lim, flags,
+                             has_task, T_steps, x0, traj, u_log, cost, done_step, total_cost, x_final, B);
+        }); });
+    });
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -651,12 +567,8 @@ int hjbx_system_create(int kind, int n, int m, double dt, const double* umin, co
     HJBX_REQUIRE(n_params == ep || (kind == HJBX_SYS_LINEAR && n_params == 2 * ep),
                  "system kind %d takes %d parameters%s, got %d", kind, ep, kind == HJBX_SYS_LINEAR ? " (or twice that with Ad, Bd)" : "", n_params);
     for (int j = 0; j < m; ++j) HJBX_REQUIRE(umin[j] <= umax[j], "umin[%d] > umax[%d]", j, j);
-    hjbx_system* s = new (std::nothrow) hjbx_system();
+    hjbx_system* s = new_system(kind, n, m, dt, umin, umax, params, n_params, nullptr);
     if (!s) return hjbx_set_error(HJBX_EINVAL, "out of host memory");
-    memset(s, 0, sizeof(*s));
-    s->kind = kind; s->n = n; s->m = m; s->dt = dt; s->n_params = n_params;
-    for (int j = 0; j < m; ++j) { s->umin[j] = umin[j]; s->umax[j] = umax[j]; }
-    for (int i = 0; i < n_params; ++i) s->p[i] = params[i];
     *out = s;
     return HJBX_OK;
 }

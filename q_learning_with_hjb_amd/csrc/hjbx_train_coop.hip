@@ -277,8 +277,8 @@ static int launch_coop_user(const hjbx_system* sysh, const hjbx_task* task, cons
         constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value;
         return launch_coop_nm<N, M>(sysh, task, mlp, x, cost, done, flat, workspace, B, st, fuse,
                                     [&](const CoopCall& c, const MlpP<N>& p, const TaskP<float, N, M>& tk, const Limits<float, M>& lim, hipStream_t s) -> int {
-            // the kernel's arguments in order; [0], the system struct, is filled in by hjbx_user_train_launch
-            void* a[] = {nullptr, (void*)&p, (void*)&tk, (void*)&lim, (void*)&c.W1, (void*)&c.W2, (void*)&c.W3, (void*)&c.x, (void*)&c.cost, (void*)&c.done,
+            auto blob = user_blob<float>(sysh);     // the kernel's arguments in order
+            void* a[] = {&blob, (void*)&p, (void*)&tk, (void*)&lim, (void*)&c.W1, (void*)&c.W2, (void*)&c.W3, (void*)&c.x, (void*)&c.cost, (void*)&c.done,
                          (void*)&c.eps_term, (void*)&c.partial, (void*)&c.partial_w1, (void*)&c.sums, (void*)&c.B, (void*)&c.ntiles};
             return hjbx_user_train_launch(sysh, mlp->activation, mode == HJBX_RESIDUAL_NORMALISED ? 0 : 1, c.psplit, (unsigned)c.grid, a, s, who);
         });

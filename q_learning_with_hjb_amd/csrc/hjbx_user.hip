@@ -33,36 +33,33 @@
 #include "hjbx_mlp_host.hpp"
 
 // ---- the header texts handed to hiprtc, embedded at build time (host pass only) ------------------------------------------------------
+// (symbol, file under csrc, the name an #include of the device units finds it by): written once; the .incbin lines, the declarations and
+// the two arrays handed to hiprtcCreateProgram (compile_unit) are generated from this list
+#define HJBX_EMBEDDED_HEADERS(X)                                                    \
+    X(hjbx_src_systems, "hjbx_systems.hpp", "hjbx_systems.hpp")                     \
+    X(hjbx_src_stream, "hjbx_stream_kernels.hpp", "hjbx_stream_kernels.hpp")        \
+    X(hjbx_src_user, "hjbx_user_kernels.hpp", "hjbx_user_kernels.hpp")              \
+    X(hjbx_src_user_mlp, "hjbx_user_mlp_kernels.hpp", "hjbx_user_mlp_kernels.hpp")  \
+    X(hjbx_src_mlp_core, "hjbx_mlp_core.hpp", "hjbx_mlp_core.hpp")                  \
+    X(hjbx_src_mlp_kernels, "hjbx_mlp_kernels.hpp", "hjbx_mlp_kernels.hpp")         \
+    X(hjbx_src_mlp_x3, "hjbx_mlp_x3.hpp", "hjbx_mlp_x3.hpp")                        \
+    X(hjbx_src_mlp_h2, "hjbx_mlp_h2.hpp", "hjbx_mlp_h2.hpp")                        \
+    X(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp", "hjbx_train_coop_kernels.hpp") \
+    X(hjbx_src_user_train, "hjbx_user_train_kernels.hpp", "hjbx_user_train_kernels.hpp") \
+    X(hjbx_src_abi, "../../include/hjbx.h", "hjbx.h")
 #if !defined(__HIP_DEVICE_COMPILE__)
 #ifndef HJBX_CSRC_DIR
 #error "compile hjbx_user.hip with -DHJBX_CSRC_DIR=\"<absolute path of csrc>\""
 #endif
-#define HJBX_EMBED(sym, file)                                                                                                     \
+#define HJBX_EMBED(sym, file, name)                                                                                               \
     asm(".pushsection .rodata\n.global " #sym "\n.type " #sym ", @object\n" #sym ":\n.incbin \"" HJBX_CSRC_DIR "/" file "\"\n.byte 0\n" \
-        ".popsection\n")
-HJBX_EMBED(hjbx_src_systems, "hjbx_systems.hpp");
-HJBX_EMBED(hjbx_src_stream, "hjbx_stream_kernels.hpp");
-HJBX_EMBED(hjbx_src_user, "hjbx_user_kernels.hpp");
-HJBX_EMBED(hjbx_src_user_mlp, "hjbx_user_mlp_kernels.hpp");
-HJBX_EMBED(hjbx_src_mlp_core, "hjbx_mlp_core.hpp");
-HJBX_EMBED(hjbx_src_mlp_kernels, "hjbx_mlp_kernels.hpp");
-HJBX_EMBED(hjbx_src_mlp_x3, "hjbx_mlp_x3.hpp");
-HJBX_EMBED(hjbx_src_mlp_h2, "hjbx_mlp_h2.hpp");
-HJBX_EMBED(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp");
-HJBX_EMBED(hjbx_src_user_train, "hjbx_user_train_kernels.hpp");
-HJBX_EMBED(hjbx_src_abi, "../../include/hjbx.h");
+        ".popsection\n");
+HJBX_EMBEDDED_HEADERS(HJBX_EMBED)
+#undef HJBX_EMBED
 #endif
-extern "C" const char hjbx_src_systems[];
-extern "C" const char hjbx_src_stream[];
-extern "C" const char hjbx_src_user[];
-extern "C" const char hjbx_src_user_mlp[];
-extern "C" const char hjbx_src_mlp_core[];
-extern "C" const char hjbx_src_mlp_kernels[];
-extern "C" const char hjbx_src_mlp_x3[];
-extern "C" const char hjbx_src_mlp_h2[];
-extern "C" const char hjbx_src_train_coop[];
-extern "C" const char hjbx_src_user_train[];
-extern "C" const char hjbx_src_abi[];
+#define HJBX_DECLARE(sym, file, name) extern "C" const char sym[];
+HJBX_EMBEDDED_HEADERS(HJBX_DECLARE)
+#undef HJBX_DECLARE
 
 // what hiprtc's built-in runtime header does not bring: the system headers the library's own headers include, as far as they use them
 static const char kStubRuntime[] = "// hip/hip_runtime.h: provided by hiprtc itself\n";
@@ -151,12 +148,14 @@ struct UserProgram {
 // out->kernel[].  Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
 int compile_unit(const Rtc& R, const char* who, const char* top, const char* unit_name, const std::string& snippet, int user_kind, int n, int m,
                  int np, const std::vector<std::string>& extra, const std::vector<const char*>& name_exprs, UserUnit* out) {
-    const char* headers[] = {hjbx_src_systems, hjbx_src_stream, hjbx_src_user, hjbx_src_user_mlp, hjbx_src_mlp_core, hjbx_src_mlp_kernels,
-                             hjbx_src_mlp_x3, hjbx_src_mlp_h2, hjbx_src_train_coop, hjbx_src_user_train, hjbx_src_abi, kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint,
-                             kStubStddef, kStubStddef, kStubTypeTraits};
-    const char* names[] = {"hjbx_systems.hpp", "hjbx_stream_kernels.hpp", "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_core.hpp",
-                           "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx.h", "hjbx_internal.hpp", "hjbx_user_snippet.hpp",
-                           "hip/hip_runtime.h", "stdint.h", "stddef.h", "cstddef", "type_traits"};
+#define HJBX_TEXT(sym, file, name) sym,
+#define HJBX_NAME(sym, file, name) name,
+    const char* headers[] = {HJBX_EMBEDDED_HEADERS(HJBX_TEXT) kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint, kStubStddef, kStubStddef,
+                             kStubTypeTraits};
+    const char* names[] = {HJBX_EMBEDDED_HEADERS(HJBX_NAME) "hjbx_internal.hpp", "hjbx_user_snippet.hpp", "hip/hip_runtime.h", "stdint.h", "stddef.h",
+                           "cstddef", "type_traits"};
+#undef HJBX_TEXT
+#undef HJBX_NAME
     static_assert(sizeof(headers) == sizeof(names), "one name per header");
     hiprtcProgram prog = nullptr;
     if (R.create(&prog, top, unit_name, (int)(sizeof(headers) / sizeof(headers[0])), headers, names) != HIPRTC_SUCCESS)
@@ -391,13 +390,8 @@ extern "C" int hjbx_system_create_from_source(int user_kind, const char* device_
         delete u;
         return rc;
     }
-    hjbx_system* s = new (std::nothrow) hjbx_system();
+    hjbx_system* s = new_system(HJBX_SYS_USER, n, m, dt, umin, umax, params, n_params, u);
     if (!s) { delete u; return hjbx_set_error(HJBX_EINVAL, "out of host memory"); }
-    memset(s, 0, sizeof(*s));
-    s->kind = HJBX_SYS_USER; s->n = n; s->m = m; s->dt = dt; s->n_params = n_params;
-    for (int j = 0; j < m; ++j) { s->umin[j] = umin[j]; s->umax[j] = umax[j]; }
-    for (int i = 0; i < n_params; ++i) s->p[i] = params[i];
-    s->user = u;
     *out = s;
     return HJBX_OK;
 }
@@ -452,12 +446,6 @@ int hjbx_user_launch(const hjbx_system* s, const char* kernel, unsigned grid, vo
 
 // ---- the matrix-core kernels of an enabled handle --------------------------------------------------------------------------------
 namespace {
-struct UserBlobF { float p[HJBX_USER_MAX_PARAMS]; };   // the kernels' first argument is `struct { float p[n_params]; }`
-UserBlobF user_blob(const hjbx_system* s) {
-    UserBlobF b;
-    for (int i = 0; i < HJBX_USER_MAX_PARAMS; ++i) b.p[i] = i < s->n_params ? (float)s->p[i] : 0.f;
-    return b;
-}
 constexpr unsigned kMcBlock = 8 * 64;   // WAVES * 64 of hjbx_user_mlp_kernels.hpp
 }  // namespace
 
@@ -466,7 +454,7 @@ int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float*
     if (int rc = matrix_core_unit(s, net.soft, net.activation, who, &unit)) return rc;
     return with_mc_dims(s, who, "matrix-core kernel", [&](auto Nc, auto) -> int {
         constexpr int N = decltype(Nc)::value;
-        UserBlobF blob = user_blob(s);
+        auto blob = user_blob<float>(s);
         MlpP<N> p = make_mlp_params<N>(net);
         int64_t ngroups = 0, grid = 0;
         if (int rc = mlp_value_grad_grid(B, 1, &ngroups, &grid, who)) return rc;
@@ -484,7 +472,7 @@ int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_ne
     if (int rc = matrix_core_unit(s, net.soft, net.activation, who, &unit)) return rc;
     return with_mc_dims(s, who, "matrix-core kernel", [&](auto Nc, auto Mc) -> int {
         constexpr int N = decltype(Nc)::value, M = decltype(Mc)::value;
-        UserBlobF blob = user_blob(s);
+        auto blob = user_blob<float>(s);
         MlpP<N> p = make_mlp_params<N>(net);
         auto tk = make_task<float, N, M>(task);
         auto lim = make_limits<float, M>(s);
@@ -512,7 +500,5 @@ int hjbx_user_train_launch(const hjbx_system* s, int activation, int mode, int p
     if (mode < 0 || mode > 1 || (psplit != 1 && psplit != 4)) return hjbx_set_error(HJBX_EINVAL, "%s: residual mode %d / psplit %d", who, mode, psplit);
     UserUnit* unit = nullptr;
     if (int rc = train_unit(s, activation, who, &unit)) return rc;
-    UserBlobF blob = user_blob(s);
-    args[0] = &blob;
     return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[2 * mode + (psplit == 4 ? 1 : 0)].c_str(), grid, 256, args, stream, who);
 }

@@ -271,3 +271,130 @@ def test_user_system_vhjb_kernels_and_fused_rollout_properties():
     ctl.epochs, ctl.num_of_trajectories_per_epoch = 2, 16
     lists = ctl.train()
     assert len(lists) == 6 and len(lists[0]) == 2 and all(np.isfinite(v) for v in lists[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_every_user_kernel_takes_the_arguments_of_its_builtin_twin(prec):
+    """Each of the 16 run-time compiled kernels of a precision once, through the host's one launch path: the user-written planar quadrotor
+    against the built-in Quadrotors2D, B = 257 (two workgroups, one live lane in the second).  Per element at 1e-12 (f64) / 1e-5 (f32) of the
+    element's own term scale -- the two differ in the rounding of f1 / f2 only; an argument packed in the wrong place or width gives garbage.
+    The fused rollout is compared step by step from ITS OWN logged states (built-in controller / simulate / costs applied to them), so the
+    per-step bounds hold without a growth factor for the closed loop."""
+    from types import SimpleNamespace
+    from parity_util import residual_term_scales, step_term_scales
+    from q_learning_with_hjb_amd.controller.quadrotors_model_based_controller import Quadrotors2DHoveringController
+    from q_learning_with_hjb_amd.dynamics.quadrotors import Quadrotors2D
+    tdt, tol = (torch.float64, 1e-12) if prec == "f64" else (torch.float32, 1e-5)
+    cfg, vc = D.quadrotors2d_dynamics_config(), make_vhjb_config("quad2d")
+    du, db = UserQuad2D(cfg), Quadrotors2D(cfg)
+    us, bs, s = du.system, db.system, O.System.from_dynamics(db)
+    B, n, m, dt, ai = 257, 6, 2, float(db.dt), [2]
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=tdt, device="cuda")
+    f64 = lambda t: t.cpu().numpy().astype(np.float64)
+    rng = np.random.default_rng(29)
+    xd, ud, gd = dev(rng.uniform(-1, 1, (B, n)) * [2.2, 2.2, 1.6, 4, 4, 2.2]), dev(rng.uniform(-25, 25, (B, m))), dev(rng.standard_normal((B, n)) * 8)
+    xr, ur, gr = f64(xd), f64(ud), f64(gd)
+    umax = np.abs(db.umax).astype(np.float64)
+
+    def affine_scales(x):       # |terms| of xdot and of one integration step from x (tests/test_gpu_parity.py: test_pointwise_kernels)
+        o1, o2 = (f64(t) for t in _ops.affine(bs, dev(x)))
+        return o1, o2, np.abs(o1).max(1, keepdims=True)
+
+    # ---- the pointwise kernels
+    o1, o2, row1 = affine_scales(xr)
+    f1, f2 = _ops.affine(us, xd)
+    check(f1, o1, tol, row1); check(f2, o2, tol, np.abs(o2).reshape(B, -1).max(1)[:, None, None])
+    check(_ops.wrap(us, xd), f64(_ops.wrap(bs, xd)), tol, np.pi, angle_idx=ai)
+    S_xd = np.abs(o1) + np.einsum("bkj,bj->bk", np.abs(o2), np.abs(ur)) + row1
+    check(_ops.dynamics_step(us, xd, ud), f64(_ops.dynamics_step(bs, xd, ud)), tol, S_xd)
+    S_sim = np.abs(xr) + dt * (np.abs(o1) + np.einsum("bkj,bj->bk", np.abs(o2), np.clip(np.abs(ur), None, umax)) + row1)
+    S_sim[:, ai] += np.pi
+    for integ in (_abi.EULER, _abi.RK4):
+        check(_ops.simulate(us, xd, ud, integ), f64(_ops.simulate(bs, xd, ud, integ)), tol, S_sim, angle_idx=ai)
+    u01 = dev(rng.uniform(size=(B, n)))
+    mean, std = np.linspace(-0.5, 0.5, n), np.linspace(0.5, 1.5, n)
+    S_x0 = np.broadcast_to(np.abs(mean) + np.abs(std), (B, n)).copy()
+    S_x0[:, ai] += np.pi
+    check(_ops.initial_state(us, mean, std, u01), f64(_ops.initial_state(bs, mean, std, u01)), tol, S_x0, angle_idx=ai)
+    task = _abi.make_task(n, m, vc.Q, vc.R, np.eye(n) * 3.0, vc.xf, vc.uf, vc.obs_min, vc.obs_max, vc.epsilon)
+    xf, uf = np.asarray(vc.xf, np.float64), np.asarray(vc.uf, np.float64)
+    Qa, Ra, Pa = np.abs(np.asarray(vc.Q, np.float64)), np.abs(np.asarray(vc.R, np.float64)), 3.0 * np.eye(n)
+
+    def cost_scales(x, u):      # |terms| of l = e'Qe + du'R du and of e'Pe, with what the cancellation in e = wrap(x - xf) contributes
+        e, xs = np.abs(O.wrap(s, x - xf[None, :])), np.abs(x) + np.abs(xf)[None, :]
+        dua = np.abs(u - uf[None, :])
+        S_l = np.einsum("bi,ij,bj->b", e, Qa, e + 2 * xs) + np.einsum("bi,ij,bj->b", dua, Ra, dua + 2 * (np.abs(u) + np.abs(uf)[None, :]))
+        return S_l, np.einsum("bi,ij,bj->b", e, Pa, e + 2 * xs)
+
+    S_l, S_term = cost_scales(xr, ur)
+    check(_ops.running_cost(us, task, xd, ud), f64(_ops.running_cost(bs, task, xd, ud)), tol, S_l)
+    check(_ops.termination_cost(us, task, xd), f64(_ops.termination_cost(bs, task, xd)), tol, S_term)
+    Rinva = np.abs(np.linalg.inv(np.asarray(vc.R, np.float64)))
+    S_u = umax[None, :] + 0.5 * np.einsum("jq,bkq,bk->bj", Rinva, np.abs(o2), np.abs(gr))
+    check(_ops.control_from_grad(us, task, xd, gd), f64(_ops.control_from_grad(bs, task, xd, gd)), tol, S_u)
+
+    # ---- the residual, both modes, with the in-kernel sums
+    done = (rng.uniform(size=B) < 0.3).astype(np.float64)
+    w = 1.0 - done
+    for mode in (_abi.RESIDUAL_NORMALISED, _abi.RESIDUAL_RAW):
+        li, dg, sums = _ops.hjb_residual(us, task, xd, gd, dev(done), mode)
+        bli, bdg, bsums = (f64(t) for t in _ops.hjb_residual(bs, task, xd, gd, dev(done), mode))
+        S_li, S_dg = residual_term_scales(db, task, s, xr, gr, mode)
+        check(li, bli, tol, S_li * w); check(dg, bdg, tol, S_dg * w[:, None])
+        got = f64(sums)
+        assert abs(got[0] - bsums[0]) <= tol * (S_li * w).sum() + tol * abs(bsums[0]), (got, bsums)
+        assert got[1] == bsums[1] and got[2] == bsums[2]
+
+    # ---- one closed-loop step of the value-gradient controller, both integrators, every optional output
+    ctl = SimpleNamespace(R=vc.R, R_inv=np.linalg.inv(np.asarray(vc.R, np.float64)), uf=vc.uf, epsilon=vc.epsilon)
+    for integ, iname in ((_abi.EULER, "euler"), (_abi.RK4, "rk4")):
+        outs = []
+        for h in (us, bs):
+            o = dict(xn=torch.empty_like(xd), u=torch.empty_like(ud), c=torch.empty(B, dtype=tdt, device="cuda"), d=torch.empty(B, dtype=tdt, device="cuda"),
+                     r=torch.zeros(B, dtype=tdt, device="cuda"), ds=torch.full((B,), -1, dtype=torch.int32, device="cuda"))
+            _ops.vhjb_step(h, task, 3, 200, xd, gd, o["xn"], o["c"], o["d"], o["ds"], u_out=o["u"], integrator=integ, resid_t=o["r"])
+            outs.append(o)
+        a, b = outs
+        ds = b["ds"].cpu().numpy()
+        assert torch.equal(a["ds"], b["ds"]) and torch.equal(a["d"], b["d"]) and 0 < (ds >= 0).sum() < B
+        S = step_term_scales("quad2d", db, ctl, s, xr, gr, np.abs(gr), f64(b["u"]), f64(b["c"]), integ=iname)
+        live = ds < 0
+        check(a["xn"], f64(b["xn"]), tol, S["x_next"], angle_idx=ai)
+        check(a["u"], f64(b["u"]), tol, S["u"])
+        check(a["c"], f64(b["c"]), tol, np.where(live, S["cost"], S_term))
+        check(a["r"], f64(b["r"]), tol, np.where(live, S["residual"], 0.0))
+
+    # ---- the feedback controller and the fused closed loop under it (T = 3, task, terminate, every log)
+    c = Quadrotors2DHoveringController(db, np.zeros(n), np.eye(n), np.eye(m))
+    desc = c._descriptor()
+    Ka = np.abs(np.asarray(c.K, np.float64)).reshape(m, n)
+    ctrl_scale = lambda x: umax[None, :] + (np.abs(x) + np.pi) @ Ka.T          # u = clip(uf - K wrap(x - xf)), xf = 0
+    check(_ops.controller(us, desc, xd), f64(_ops.controller(bs, desc, xd)), tol, ctrl_scale(xr))
+    T = 3
+    for integ in (_abi.EULER, _abi.RK4):
+        a = _ops.rollout_feedback(us, desc, xd, T, task=task, integrator=integ, terminate=True, log_u=True, log_cost=True)
+        b = _ops.rollout_feedback(bs, desc, xd, T, task=task, integrator=integ, terminate=True, log_u=True, log_cost=True)
+        assert torch.equal(a["done_step"], b["done_step"])
+        ds = a["done_step"].cpu().numpy()
+        assert (ds == 0).any() and ((ds > 0) & (ds < T)).any() and (ds == T).any()
+        assert torch.equal(a["traj"][0], xd) and torch.equal(a["x_final"], a["traj"][T])
+        for t in range(T + 1):
+            xt = a["traj"][t]
+            xtr = f64(xt)
+            live, now = torch.as_tensor(ds > t, device="cuda"), ds == t
+            if t < T:
+                ut = a["u"][t]
+                assert not ut[~live].any() and torch.equal(a["traj"][t + 1][~live], xt[~live])          # stopped: no control, the state stays
+                lv = ds > t
+                check(ut[live], f64(_ops.controller(bs, desc, xt))[lv], tol, ctrl_scale(xtr)[lv])
+                q1, q2, r1 = affine_scales(xtr)
+                S_step = np.abs(xtr) + dt * (np.abs(q1) + np.einsum("bkj,bj->bk", np.abs(q2), np.abs(f64(ut))) + r1)
+                S_step[:, ai] += np.pi
+                check(a["traj"][t + 1][live], f64(_ops.simulate(bs, xt, ut, integ))[lv], tol, S_step[lv], angle_idx=ai)
+            S_l, S_term = cost_scales(xtr, f64(a["u"][t]) if t < T else np.zeros((B, m)))
+            want = np.where(now, f64(_ops.termination_cost(bs, task, xt)), 0.0)
+            if t < T:
+                want = np.where(ds > t, f64(_ops.running_cost(bs, task, xt, a["u"][t])) * dt, want)
+            check(a["cost"][t], want, tol, np.where(now, S_term, np.where(ds > t, S_l * dt, 0.0)))
+        check(a["total_cost"], f64(a["cost"]).sum(0), tol, np.abs(f64(a["cost"])).sum(0))

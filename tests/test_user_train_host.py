@@ -259,7 +259,9 @@ def test_header_and_bindings_declare_the_train_unit():
         doc = hdr[hdr.index(begins):hdr.index(f"int {entry}(")]                                  # what the header says at this entry point
         assert "hjbx_system_enable_matrix_cores" in doc and "scratch" in doc and "HJBX_OPT_TRAIN_KERNEL" in doc, entry
     embedded = open(os.path.join(CSRC, "hjbx_user.hip")).read()
-    assert 'HJBX_EMBED(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp")' in embedded
+    # (one list of embedded headers: symbol, file, the name hiprtc sees; the .incbin lines and the arrays handed to hiprtc come from it)
+    assert 'X(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp", "hjbx_train_coop_kernels.hpp")' in embedded
+    assert "HJBX_EMBEDDED_HEADERS(HJBX_EMBED)" in embedded and "HJBX_EMBEDDED_HEADERS(HJBX_TEXT)" in embedded and "HJBX_EMBEDDED_HEADERS(HJBX_NAME)" in embedded
     unit = open(os.path.join(CSRC, "hjbx_user_train_kernels.hpp")).read()
     assert "#define HJBX_USER_MATRIX_CORE_UNIT 1" in unit and unit.count("template __global__ void HJBX_UT_") == 4
 
