@@ -385,6 +385,23 @@ int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const
                             int n_steps, int T_max, const float* x, float* traj, float* u_log, float* cost, float* done, float* resid,
                             int32_t* done_step, float* x_out, const int32_t* env_order, int64_t B, void* workspace, void* stream);
 
+/* The Hessian of the PD value network (hjbx_mlp) with respect to the state, and the Jacobian of its last layer: what the reference takes
+ * from jax.hessian / jax.jacobian in utils/debug_helper.py:40-59 (local_optimal_x) and :7-38 (the equivalent linear map of a ReLU network),
+ * and what the landscape plots of utils/debug_plots.py:145-172 are drawn from.
+ *   H (B,n,n) or NULL:      H[b,i,j] = d2V / dx_i dx_j at x_b = diag(1/std) H_z diag(1/std) + 2 eps_scalar I, with
+ *                           H_z = 2 J_z J_z' + A2. diag(r2 . act''(a2)) A2.' + A1. diag(r1 . act''(a1)) A1.'  (J_z = dy/dz, A1. = da1/dz, A2. = da2/dz,
+ *                           r2, r1 the reverse sweep of hjbx_value_grad_f32; act'' = 0 for relu, -2h(1-h^2) for tanh, -h for sin).
+ *   dy_dx (B,n,h3) or NULL: dy_dx[b,i,:] = dy / de_i, y the output of the last layer, e = wrap(x - xf) the error coordinates.
+ * The wrap is data (d wrap = I), as in hjbx_value_grad_f32.  For relu H is piecewise constant and both outputs jump where a hidden unit
+ * crosses zero.  H is computed column by column (each column is one tangent sweep through the network): it is symmetric up to rounding and
+ * NOT bitwise symmetric.  Results are deterministic: two calls on the same input agree bit for bit.
+ * Always the float32 MFMA arithmetic (HJBX_OPT_MLP_ARITHMETIC does not apply).  Features [128,128,64]; relu, tanh and sin; the built-in
+ * systems hjbx_value_grad_f32 dispatches.  A user-defined system (HJBX_SYS_USER) returns HJBX_EUNSUPPORTED.  No workspace.
+ * x must be aligned to its row vector width, H and dy_dx to 16 bytes.  B == 0 or both outputs NULL: HJBX_OK, nothing is launched. */
+#define HJBX_HAS_VALUE_HESSIAN 1 /* the entry point below exists (an addition, nothing else changed) */
+int hjbx_value_hessian_f32(const hjbx_system* sys, const hjbx_mlp* mlp, const float* x, float* H /* (B,n,n) or NULL */,
+                           float* dy_dx /* (B,n,h3) or NULL */, int64_t B, void* stream);
+
 /* The parameter gradient of one value-learning step (vhjb.py:227-253 and the jax.grad calls of :282-284) for a minibatch of B samples
  * (x (B,n), cost (B,), done (B,) as 0/1 floats), fused on the matrix cores:
  *   flat = [ d(sum_b hjb_loss_b)/dW1 (n,h1) | /dW2 (h1,h2) | /dW3 (h2,h3) | d(sum_b termination_loss_b)/dW1 | /dW2 | /dW3 |

@@ -337,6 +337,17 @@ def value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
     return V, g
 
 
+def value_hessian(sys, mlp_desc, x, want_hessian=True, want_jacobian=False):
+    """hjbx_value_hessian_f32: H (B, n, n) = d2V/dx2 and dy_dx (B, n, h3) = d(last layer)/d(error coordinates) of the PD value network on the
+    matrix cores (f32 only; None for an output that is not asked for)."""
+    B = x.shape[0]
+    _chk(x, "x", (B, sys.n), torch.float32)
+    H = torch.empty((B, sys.n, sys.n), dtype=x.dtype, device=x.device) if want_hessian else None
+    J = torch.empty((B, sys.n, int(mlp_desc.h3)), dtype=x.dtype, device=x.device) if want_jacobian else None
+    check(lib().hjbx_value_hessian_f32(sys.ptr, ref(mlp_desc), _p(x), _p(H), _p(J), B, _stream()))
+    return H, J
+
+
 def softpd_value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
     """value_grad for the soft-PD network (mlp_desc: _abi.HjbxSoftpdMlp): hjbx_softpd_value_grad_f32."""
     B = x.shape[0]

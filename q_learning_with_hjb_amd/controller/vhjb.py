@@ -152,6 +152,50 @@ class ValueFunctionApproximator(torch.nn.Module):
             assert w.is_contiguous() and w.dtype == torch.float32
         return _ops.value_grad(self.dynamics.system, self.descriptor(), x, want_v, want_grad)
 
+    # act''(a): zero for relu (the Hessian of a ReLU network is piecewise constant)
+    _D2ACT = {"relu": lambda a: torch.zeros_like(a),
+              "sin": lambda a: -torch.sin(a),
+              "tanh": lambda a: -2.0 * torch.tanh(a) * (1.0 - torch.tanh(a) ** 2)}
+
+    @torch.no_grad()
+    def value_hessian(self, x: torch.Tensor, want_jacobian: bool = False):
+        """d2V/dx2 (B, n, n) in closed form, in torch operations on the module's device and in its dtype (what jax.hessian of the value
+        function gives in the reference's utils/debug_helper.py; the wrap is data):
+            H_z = 2 J J' + A2 diag(r2 act''(a2)) A2' + A1 diag(r1 act''(a1)) A1',   H_x = H_z / (std std') + 2 eps_s I
+        with J = dy/dz, A1 = da1/dz, A2 = da2/dz and r2, r1 the reverse sweep of value_and_grad.  It serves float64 networks and whatever
+        the fused kernel refuses.  want_jacobian: -> (H, dy/de (B, n, h3))."""
+        W1, W2, W3 = self.weights
+        e = self.error_coords(x)
+        z = (e - self.mean) / self.std
+        act, dact = self._ACT[self.activation]
+        d2act = self._D2ACT[self.activation]
+        a1 = z @ W1
+        a2 = act(a1) @ W2
+        y = act(a2) @ W3
+        s1, s2 = dact(a1), dact(a2)
+        A1 = W1.unsqueeze(0)                                   # (1, n, h1)
+        A2 = (A1 * s1.unsqueeze(1)) @ W2                       # (B, n, h2)
+        J = (A2 * s2.unsqueeze(1)) @ W3                        # (B, n, h3)
+        r2 = (2.0 * y) @ W3.t()
+        r1 = (r2 * s2) @ W2.t()
+        Hz = 2.0 * (J @ J.transpose(1, 2))
+        if self.activation != "relu":
+            Hz = Hz + (A2 * (r2 * d2act(a2)).unsqueeze(1)) @ A2.transpose(1, 2) + (A1 * (r1 * d2act(a1)).unsqueeze(1)) @ A1.transpose(1, 2)
+        n = e.shape[-1]
+        H = Hz / (self.std.unsqueeze(0) * self.std.unsqueeze(1)) + (2.0 * self.epsilon_scalar) * torch.eye(n, dtype=Hz.dtype, device=Hz.device)
+        return (H, J / self.std.unsqueeze(-1)) if want_jacobian else H
+
+    @torch.no_grad()
+    def fused_value_hessian(self, x: torch.Tensor, want_jacobian: bool = False):
+        """d2V/dx2 (B, n, n) from the matrix-core kernel hjbx_value_hessian_f32 (float32; columns are computed one by one, so H is symmetric up
+        to rounding only).  want_jacobian: -> (H, dy/de (B, n, h3)), the Jacobian of the last layer in error coordinates."""
+        if self.activation not in self.FUSED_ACTIVATIONS:
+            raise NotImplementedError(f"no fused Hessian kernel for the {self.activation} activation")
+        for w in self.weights:
+            assert w.is_contiguous() and w.dtype == torch.float32
+        H, J = _ops.value_hessian(self.dynamics.system, self.descriptor(), x, True, want_jacobian)
+        return (H, J) if want_jacobian else H
+
 
 class SoftPDValueFunctionApproximator(torch.nn.Module):
     """The notebooks' second value network (SoftPDValueApproximator: examples/cartpole_balancing.ipynb cell 6, drone_hovering.ipynb cell 6,
@@ -588,6 +632,17 @@ class VHJBController(Controller):
         if self.fused_value_grad and x.dtype == torch.float32:
             return self.value_function_approximator.fused_value_grad(x, want_v=False)[1]
         return self.value_function_approximator.value_and_grad(x)[1]
+
+    @torch.no_grad()
+    def value_hessian(self, x: torch.Tensor) -> torch.Tensor:
+        """d2V/dx2 (B, n, n) for a (B, n) device batch: the matrix-core kernel where this controller runs the fused value network, the torch
+        closed form of ValueFunctionApproximator.value_hessian otherwise."""
+        if self.value_structure != "pd":
+            raise NotImplementedError("value_hessian exists for the PD value network only (value_structure='pd')")
+        vf = self.value_function_approximator
+        if self.fused_value_grad and x.dtype == torch.float32 and self.dynamics.system.kind != _abi.SYS_USER:
+            return vf.fused_value_hessian(x)
+        return vf.value_hessian(x)
 
     @torch.no_grad()
     def get_control_efforts_with_additional_term(self, x) -> Tuple[torch.Tensor, torch.Tensor]:

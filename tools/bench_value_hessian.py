@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Time of the value-network Hessian kernel (hjbx_value_hessian_f32) next to the torch closed form a user would otherwise run
+(ValueFunctionApproximator.value_hessian in float32 on the same device).
+
+Cart-pole (n = 4) and near-hover quadcopter (n = 10), B = 2^17 states, tanh and ReLU, H only.  The inputs rotate through --buffers state
+buffers (no launch re-reads what the previous one left in the caches); after --warmup untimed rounds each timing is a device-event window
+around --inner launches, and the figure is the median of --reps windows.  Written to profiles/value_hessian.json under "timing" (the parity
+ratios of tests/test_gpu_value_hessian.py sit under "parity" in the same file) and printed as one JSON line:
+
+  ms per launch, states/s, flop per state of the formulation (every chain a column runs, times the n columns of a state; the 32 - C n idle
+  columns of a tile are NOT counted, so the fraction below is that of useful work), that over the 157.3 TFLOP/s float32 MFMA peak, and the
+  speed-up over the torch form.
+
+    python tools/bench_value_hessian.py [--batch 131072] [--reps 10] [--inner 20] [--warmup 2] [--buffers 4]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from q_learning_with_hjb_amd.configs import defaults as D  # noqa: E402
+from q_learning_with_hjb_amd.controller.vhjb import VHJBController  # noqa: E402
+from q_learning_with_hjb_amd.dynamics.cartpole import Cartpole  # noqa: E402
+from q_learning_with_hjb_amd.dynamics.quadrotors import NearHoverQuadcopter  # noqa: E402
+
+CASES = [("cartpole", "tanh"), ("cartpole", "relu"), ("nearhover", "tanh"), ("nearhover", "relu")]
+PEAK_F32_MFMA = 157.3e12
+
+
+def flop_per_state(n, activation):
+    """What the kernel's formulation computes for one state: n columns, each its chains (2 flop per multiply-add) and the last product."""
+    smooth = activation != "relu"
+    layer1 = (4 if smooth else 3) * 2 * 128 * n                  # a1, a1. (again for act''), a1 again for the last product
+    wide = (2 + (2 if smooth else 1)) * 2 * 128 * 128            # a2, a2.; r1. (and the sample's r1)
+    narrow = 2 * (2 if smooth else 1) * 2 * 128 * 64             # y. (and y); r2. (and r2)
+    return n * (layer1 + wide + narrow + 2 * 128 * n)
+
+
+def make(name, activation):
+    if name == "cartpole":
+        d, cfg = Cartpole(D.cartpole_dynamics_config()), D.cartpole_vhjb_config()
+    else:
+        d, cfg = NearHoverQuadcopter(D.near_hover_dynamics_config()), D.near_hover_vhjb_config()
+    ctl = VHJBController(d, cfg, activation=activation, graph_updates=False)     # lecun-normal weights from the config's seed
+    return d, ctl
+
+
+def median_ms(fn, xs, warmup, reps, inner):
+    k = 0
+    for _ in range(warmup * len(xs)):
+        fn(xs[k % len(xs)])
+        k += 1
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(inner):
+            out = fn(xs[k % len(xs)])
+            k += 1
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) / inner)
+        del out
+    return float(np.median(times)), float(np.min(times)), float(np.max(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1 << 17)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--inner", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--buffers", type=int, default=4)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "value_hessian.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_value_hessian: needs an MI355X (there is no CPU path to time)")
+    res = {}
+    for name, act in CASES:
+        d, ctl = make(name, act)
+        vf = ctl.value_function_approximator
+        n = d.state_dim
+        rng = np.random.default_rng(0)
+        box = np.asarray(ctl.obs_max, np.float64).clip(max=3.0)
+        xs = [torch.as_tensor(np.asarray(ctl.xf, np.float64) + rng.uniform(-1, 1, (args.batch, n)) * box, dtype=torch.float32, device="cuda").contiguous()
+              for _ in range(args.buffers)]
+        Hk, Ht = vf.fused_value_hessian(xs[0]), vf.value_hessian(xs[0])
+        scale = Ht.abs().amax(dim=(1, 2), keepdim=True)
+        agree = float(((Hk - Ht).abs() / scale).max().item())          # the two float32 evaluations timed here compute the same thing
+        del Hk, Ht, scale
+        k_ms, k_lo, k_hi = median_ms(vf.fused_value_hessian, xs, args.warmup, args.reps, args.inner)
+        t_ms, t_lo, t_hi = median_ms(vf.value_hessian, xs, args.warmup, args.reps, max(1, args.inner // 10))
+        flop = flop_per_state(n, act)
+        res[f"{name}_{act}"] = dict(n=n, kernel_ms=round(k_ms, 4), kernel_ms_min_max=[round(k_lo, 4), round(k_hi, 4)],
+                                    states_per_s=round(args.batch / (k_ms * 1e-3), 1), flop_per_state=flop,
+                                    fraction_of_f32_mfma_peak=round(flop * args.batch / (k_ms * 1e-3) / PEAK_F32_MFMA, 4),
+                                    torch_ms=round(t_ms, 4), torch_ms_min_max=[round(t_lo, 4), round(t_hi, 4)],
+                                    speedup_over_torch=round(t_ms / k_ms, 2), max_kernel_vs_torch_rel=agree)
+        del ctl, xs
+        torch.cuda.empty_cache()
+    timing = dict(tool="bench_value_hessian", B=args.batch, reps=args.reps, inner=args.inner, warmup=args.warmup, buffers=args.buffers,
+                  device=torch.cuda.get_device_name(0), peak_f32_mfma_flops=PEAK_F32_MFMA, cases=res)
+    old = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            old = json.load(f)
+    old["timing"] = timing
+    with open(args.out, "w") as f:
+        json.dump(old, f, indent=1, sort_keys=True)
+    print(json.dumps(timing))
+
+
+if __name__ == "__main__":
+    main()
