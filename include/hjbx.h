@@ -402,6 +402,27 @@ int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const
 int hjbx_value_hessian_f32(const hjbx_system* sys, const hjbx_mlp* mlp, const float* x, float* H /* (B,n,n) or NULL */,
                            float* dy_dx /* (B,n,h3) or NULL */, int64_t B, void* stream);
 
+/* The Hessian of the soft-PD value network (hjbx_softpd_mlp) with respect to the state: what jax.hessian over the value function gives in
+ * the reference's utils/debug_helper.py:40-59 (local_optimal_x) when the controller carries the notebooks' SoftPDValueApproximator.
+ *   e = wrap(x - xf); z = (e - mean)/std; a1 = z W1 + b1; h1 = act(a1); a2 = h1 W2 + b2; h2 = act(a2); a3 = h2 W3 + b3; V = act(a3) . w4 + b4
+ *   reverse sweep:  d3 = w4 . act'(a3); r2 = d3 W3'; d2 = r2 . act'(a2); r1 = d2 W2'; d1 = r1 . act'(a1); dV/dz = d1 W1'
+ *   tangent along z_j:  a1. = W1[j,:]; h1. = act'(a1) . a1.; a2. = h1. W2; h2. = act'(a2) . a2.; a3. = h2. W3
+ *                       d3. = w4 . act''(a3) . a3.; r2. = d3. W3'; d2. = r2. . act'(a2) + r2 . act''(a2) . a2.; r1. = d2. W2'
+ *                       d1. = r1. . act'(a1) + r1 . act''(a1) . a1.;  H_z[:,j] = d1. W1'
+ *   H (B,n,n):  H[b,i,j] = d2V / dx_i dx_j at x_b = diag(1/std) H_z diag(1/std)   (no eps term in this network), in closed form
+ *               H_z = A3 diag(w4 . act''(a3)) A3' + A2 diag(r2 . act''(a2)) A2' + A1 diag(r1 . act''(a1)) A1',
+ *               A1 = W1, A2 = (A1 . act'(a1)) W2, A3 = (A2 . act'(a2)) W3.
+ * The wrap is data (d wrap = I).  H is computed column by column: it is symmetric up to rounding, not bitwise.  Two calls on the same input
+ * agree bit for bit.  ReLU has act'' = 0, so the scalar piecewise-linear network has H = 0 wherever it is defined: there is no ReLU kernel,
+ * the entry point fills H with zeros on the stream.  tanh and sin run on the matrix cores (float32 MFMA; HJBX_OPT_MLP_ARITHMETIC does not
+ * apply) for the built-in systems hjbx_softpd_value_grad_f32 dispatches; a (system, activation) pair whose kernel would need scratch is
+ * refused with HJBX_EUNSUPPORTED and a message that names it (none at present).  A user-defined system returns HJBX_EUNSUPPORTED.
+ * Features [128,128,64].  No workspace.  x must be aligned to its row vector width, H to 16 bytes.  B == 0 or H == NULL: HJBX_OK, nothing
+ * is launched. */
+#define HJBX_HAS_SOFTPD_VALUE_HESSIAN 1 /* the entry point below exists (an addition, nothing else changed) */
+int hjbx_softpd_value_hessian_f32(const hjbx_system* sys, const hjbx_softpd_mlp* mlp, const float* x, float* H /* (B,n,n) */, int64_t B,
+                                  void* stream);
+
 /* The parameter gradient of one value-learning step (vhjb.py:227-253 and the jax.grad calls of :282-284) for a minibatch of B samples
  * (x (B,n), cost (B,), done (B,) as 0/1 floats), fused on the matrix cores:
  *   flat = [ d(sum_b hjb_loss_b)/dW1 (n,h1) | /dW2 (h1,h2) | /dW3 (h2,h3) | d(sum_b termination_loss_b)/dW1 | /dW2 | /dW3 |

@@ -54,9 +54,11 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_hessian.hip", ("-DHJBX_HESS_ACT=0",), "hjbx_hessian_relu.o"),   # value-network Hessian: once per activation too
           ("hjbx_hessian.hip", ("-DHJBX_HESS_ACT=1",), "hjbx_hessian_tanh.o"),
           ("hjbx_hessian.hip", ("-DHJBX_HESS_ACT=2",), "hjbx_hessian_sin.o"),
+          ("hjbx_softpd_hessian.hip", ("-DHJBX_SOFTPD_HESS_ACT=1",), "hjbx_softpd_hessian_tanh.o"),   # soft-PD Hessian: tanh + the C entry point, sin (relu: H = 0)
+          ("hjbx_softpd_hessian.hip", ("-DHJBX_SOFTPD_HESS_ACT=2",), "hjbx_softpd_hessian_sin.o"),
           ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds the device headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
-_HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
+_HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_hessian_kernels.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
             "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
@@ -257,7 +259,7 @@ EXPORTED_SYMBOLS = (
      "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32", "hjbx_softpd_value_grad_f32", "hjbx_softpd_rollout_f32",
      "hjbx_replay_append_workspace_bytes", "hjbx_replay_append_f32", "hjbx_replay_append_f64",
      "hjbx_initial_state_philox_f32", "hjbx_initial_state_philox_f64", "hjbx_rollout_cost_stats_f32", "hjbx_rollout_cost_stats_f64",
-     "hjbx_activation_probe_f32", "hjbx_value_hessian_f32"]
+     "hjbx_activation_probe_f32", "hjbx_value_hessian_f32", "hjbx_softpd_value_hessian_f32"]
     + [f"hjbx_{k}_{s}" for k in _typed_signatures() for s in ("f32", "f64")]
 )
 
@@ -307,6 +309,8 @@ def lib() -> C.CDLL:
         L.hjbx_value_grad_f32.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _VP]
         L.hjbx_value_hessian_f32.restype = C.c_int
         L.hjbx_value_hessian_f32.argtypes = [_VP, _VP, _VP, _VP, _VP, _I64, _VP]
+        L.hjbx_softpd_value_hessian_f32.restype = C.c_int
+        L.hjbx_softpd_value_hessian_f32.argtypes = [_VP, _VP, _VP, _VP, _I64, _VP]
         L.hjbx_vhjb_rollout_f32.restype = C.c_int
         L.hjbx_vhjb_rollout_f32.argtypes = [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]
         L.hjbx_softpd_value_grad_f32.restype = C.c_int

@@ -358,6 +358,19 @@ def softpd_value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
     return V, g
 
 
+def softpd_value_hessian(sys, mlp_desc, x):
+    """hjbx_softpd_value_hessian_f32: H (B, n, n) = d2V/dx2 of the soft-PD value network (mlp_desc: _abi.HjbxSoftpdMlp) on the matrix cores
+    (f32 only; relu: zeros).  ValueError for a wrong shape or dtype, NotImplementedError for what the library refuses (a user-defined
+    system, a (system, activation) pair it does not ship)."""
+    B = x.shape[0]
+    if x.dtype != torch.float32:
+        raise ValueError(f"x has dtype {x.dtype}, expected {torch.float32}")
+    _chk(x, "x", (B, sys.n), torch.float32)
+    H = torch.empty((B, sys.n, sys.n), dtype=x.dtype, device=x.device)
+    check(lib().hjbx_softpd_value_hessian_f32(sys.ptr, ref(mlp_desc), _p(x), _p(H), B, _stream()))
+    return H
+
+
 def vhjb_rollout(sys, task, mlp_desc, x, n_steps, T_max, done_step, t_first=0, integrator=_abi.EULER, log_traj=True, log_u=False,
                  log_residual=False, want_x_out=False, env_order=None, out=None):
     """`n_steps` closed-loop VHJB steps (value gradient + step) in ONE kernel launch (f32).  `done_step` (B,) int32 is

@@ -287,6 +287,43 @@ class SoftPDValueFunctionApproximator(torch.nn.Module):
             assert w.is_contiguous() and w.dtype == torch.float32
         return _ops.softpd_value_grad(self.dynamics.system, self.descriptor(), x, want_v, want_grad)
 
+    @torch.no_grad()
+    def value_hessian(self, x: torch.Tensor) -> torch.Tensor:
+        """d2V/dx2 (B, n, n) in closed form, in torch operations on the module's device and in its dtype (the wrap is data)."""
+        return self.value_hessian_error(self.error_coords(x))
+
+    @torch.no_grad()
+    def value_hessian_error(self, e: torch.Tensor) -> torch.Tensor:
+        """value_hessian at given error coordinates e = wrap(x - xf) (B, n): what jax.hessian of the value function gives in the reference's
+        utils/debug_helper.py for this network,
+            H_z = A3 diag(w4 act''(a3)) A3' + A2 diag(r2 act''(a2)) A2' + A1 diag(r1 act''(a1)) A1',   H_x = H_z / (std std')
+        with A1 = da1/dz = W1, A2 = da2/dz, A3 = da3/dz and r2, r1 the reverse sweep of value_and_grad_error.  It serves float64 networks
+        and whatever the fused kernel refuses.  relu: act'' = 0, H = 0."""
+        W1, b1, W2, b2, W3, b3, w4, b4 = self.layers
+        z = (e - self.mean) / self.std
+        act, dact = self._ACT[self.activation]
+        d2act = ValueFunctionApproximator._D2ACT[self.activation]
+        a1 = z @ W1 + b1
+        a2 = act(a1) @ W2 + b2
+        a3 = act(a2) @ W3 + b3
+        s1, s2 = dact(a1), dact(a2)
+        A1 = W1.unsqueeze(0)                                   # (1, n, h1)
+        A2 = (A1 * s1.unsqueeze(1)) @ W2                       # (B, n, h2)
+        A3 = (A2 * s2.unsqueeze(1)) @ W3                       # (B, n, h3)
+        r2 = (w4[:, 0] * dact(a3)) @ W3.t()
+        r1 = (r2 * s2) @ W2.t()
+        Hz = ((A3 * (w4[:, 0] * d2act(a3)).unsqueeze(1)) @ A3.transpose(1, 2) + (A2 * (r2 * d2act(a2)).unsqueeze(1)) @ A2.transpose(1, 2)
+              + (A1 * (r1 * d2act(a1)).unsqueeze(1)) @ A1.transpose(1, 2))
+        return Hz / (self.std.unsqueeze(0) * self.std.unsqueeze(1))
+
+    @torch.no_grad()
+    def fused_value_hessian(self, x: torch.Tensor) -> torch.Tensor:
+        """d2V/dx2 (B, n, n) from the matrix-core kernel hjbx_softpd_value_hessian_f32 (float32; columns are computed one by one, so H is
+        symmetric up to rounding only; relu: zeros).  NotImplementedError for what the library refuses."""
+        for w in self.layers:
+            assert w.is_contiguous() and w.dtype == torch.float32
+        return _ops.softpd_value_hessian(self.dynamics.system, self.descriptor(), x)
+
 
 # ------------------------------------------------------------------------------------------------
 # autograd bridges to the residual kernels (forward value + analytic first derivative)
@@ -635,13 +672,16 @@ class VHJBController(Controller):
 
     @torch.no_grad()
     def value_hessian(self, x: torch.Tensor) -> torch.Tensor:
-        """d2V/dx2 (B, n, n) for a (B, n) device batch: the matrix-core kernel where this controller runs the fused value network, the torch
-        closed form of ValueFunctionApproximator.value_hessian otherwise."""
-        if self.value_structure != "pd":
-            raise NotImplementedError("value_hessian exists for the PD value network only (value_structure='pd')")
+        """d2V/dx2 (B, n, n) for a (B, n) device batch, for either value network: the matrix-core kernel where this controller runs the fused
+        value network, the torch closed form of the module's value_hessian otherwise -- and for a soft-PD (system, activation) pair the
+        library refuses."""
         vf = self.value_function_approximator
         if self.fused_value_grad and x.dtype == torch.float32 and self.dynamics.system.kind != _abi.SYS_USER:
-            return vf.fused_value_hessian(x)
+            try:
+                return vf.fused_value_hessian(x)
+            except NotImplementedError:
+                if self.value_structure != "soft_pd":      # (the PD unit ships every pair: nothing to fall back from)
+                    raise
         return vf.value_hessian(x)
 
     @torch.no_grad()

@@ -32,6 +32,7 @@
 #include "hjbx_systems.hpp"
 #include "hjbx_host.hpp"
 #include "hjbx_mlp_core.hpp"
+#include "hjbx_hessian_kernels.hpp"   // mlp_value_hessian: one column of a tile (shared with hjbx_softpd_hessian.hip)
 #include "hjbx_mlp_host.hpp"
 
 using namespace hjbx;
@@ -43,224 +44,6 @@ using namespace hjbx;
 static constexpr int kAct = HJBX_HESS_ACT;
 static_assert(kAct == HJBX_ACT_RELU || kAct == HJBX_ACT_TANH || kAct == HJBX_ACT_SIN, "the Hessian kernel exists for relu, tanh and sin");
 static constexpr int kHessWaves = 4;   // one wave per SIMD: up to 512 registers each
-
-// One column of a tile: the state row of its sample in xs (every column computes; `j` is its direction, 0 for an idle column), `sj` = 1 / std_j.
-// dyp: this lane's part of row j of dy_dx (its 8 float4s at 32 ob + 8 q, already offset by 4 h floats), or NULL.  On return, if want_h,
-// Hcol[k] = H_x[k][j] in both lane halves.
-template <typename S, int ACT>
-__device__ __forceinline__ void mlp_value_hessian(const S& sys, const MlpP<S::N>& p, const MlpCtx& c, const float (&xs)[S::N], int j, float sj,
-                                                  bool want_h, float* __restrict__ dyp, float (&Hcol)[S::N]) {
-    constexpr int N = S::N;
-    constexpr int NP = MlpLds<N>::NP;
-    constexpr bool kSmooth = ACT != HJBX_ACT_RELU;   // act'' != 0: the sample's reverse sweep (r2, r1) enters the Hessian
-    constexpr bool kSin = ACT == HJBX_ACT_SIN;
-    const int h = c.h;
-    float e[N], z[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) e[k] = xs[k] - p.xf[k];
-    sys.wrap(e);
-#pragma unroll
-    for (int k = 0; k < N; ++k) z[k] = (e[k] - p.mean[k]) * p.istd[k];
-    float ring4[3][4], ring2[3][2];  // operand rings of the chains (DEPTH = 2)
-    // One element-wise evaluation at a time for the smooth activations: left alone the scheduler interleaves the 64 independent polynomial
-    // evaluations of a pass and their temporaries spill (see mlp_value_grad).
-    auto fence = [&](float& v) {
-        if constexpr (kSmooth) {
-            asm volatile("" : "+v"(v));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    auto getz = [&](int st, int) { return h ? z[2 * st + 1] : z[2 * st]; };
-    auto getej = [&](int st, int) { return (2 * st + h) == j ? 1.0f : 0.0f; };   // the unit vector e_j: the chain then returns W1[j,:] exactly
-
-    // ---- layer 1 and its tangent: h1 = act(a1), a2 = h1 W2;  a1. = W1[j,:], h1. = act'(a1) . a1. ------------------------------------------
-    f32x16 a1[1][4];
-    zero_acc(a1);
-    mfma_chain<OffW1F, N / 2, 4, 2, 1>(a1, ring4, c.w1f, getz);
-    f32x16 c1[1][kSin ? 4 : 1];   // sin only: cos(a1), until h1. is formed
-#pragma unroll
-    for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (kSin) {
-                float sn, cs;
-                sincos1(a1[0][fb][r], sn, cs);
-                asm volatile("" : "+v"(sn), "+v"(cs));
-                a1[0][fb][r] = sn;
-                c1[0][kSin ? fb : 0][r] = cs;
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                float v = act1<ACT>(a1[0][fb][r]);
-                fence(v);
-                a1[0][fb][r] = v;
-            }
-        }
-    f32x16 a2[1][4];   // after its pass below: h2 = act(a2) (sin: sin(a2), with cos(a2) in c2)
-    zero_acc(a2);
-    mfma_chain<OffW2F, 64, 4, 2, 1>(a2, ring4, c.w2f, [&](int st, int) { return a1[0][st >> 4][st & 15]; });
-    f32x16 t1[1][4];
-    zero_acc(t1);
-    mfma_chain<OffW1F, N / 2, 4, 2, 1>(t1, ring4, c.w1f, getej);
-#pragma unroll
-    for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t1[0][fb][r] = dact1<ACT>(kSin ? c1[0][kSin ? fb : 0][r] : a1[0][fb][r], t1[0][fb][r]);
-
-    // ---- layer 2 and its tangent: h2 = act(a2);  a2. = h1. W2, h2. = act'(a2) . a2., y. = h2. W3 ---------------------------------------------
-    f32x16 c2[1][kSin ? 4 : 1];
-#pragma unroll
-    for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (kSin) {
-                float sn, cs;
-                sincos1(a2[0][fb][r], sn, cs);
-                asm volatile("" : "+v"(sn), "+v"(cs));
-                a2[0][fb][r] = sn;
-                c2[0][kSin ? fb : 0][r] = cs;
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                float v = act1<ACT>(a2[0][fb][r]);
-                fence(v);
-                a2[0][fb][r] = v;
-            }
-        }
-    // act'(a2) . d in terms of what is kept of layer 2
-    auto dact2 = [&](int fb, int r, float d) { return dact1<ACT>(kSin ? c2[0][kSin ? fb : 0][r] : a2[0][fb][r], d); };
-    // The element-wise passes between the chains touch at most three 64-register quantities each and are fenced from one another: what a
-    // pass works on has to sit in the architectural half of the register file, the rest waits in the accumulation half.
-    f32x16 t2[1][4];   // a2.; later act''(a2) . a2., then q2 = r2 . act''(a2) . a2.
-    zero_acc(t2);
-    mfma_chain<OffW2F, 64, 4, 2, 1>(t2, ring4, c.w2f, [&](int st, int) { return t1[0][st >> 4][st & 15]; });
-#pragma unroll
-    for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t1[0][fb][r] = dact2(fb, r, t2[0][fb][r]);   // h2. (h1. is dead)
-    f32x16 yd[1][2];
-    zero_acc(yd);
-    mfma_chain<OffW3F, 64, 2, 2, 1>(yd, ring2, c.w3f, [&](int st, int) { return t1[0][st >> 4][st & 15]; });
-    // registers 4q .. 4q + 3 of block ob are the outputs 32 ob + 8 q + 4 h + 0..3: one float4
-    if (dyp) {
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4*>(dyp + 32 * ob + 8 * q) =
-                    make_float4(yd[0][ob][4 * q] * sj, yd[0][ob][4 * q + 1] * sj, yd[0][ob][4 * q + 2] * sj, yd[0][ob][4 * q + 3] * sj);
-    }
-    if (!want_h) return;
-#pragma unroll
-    for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) yd[0][ob][r] = yd[0][ob][r] + yd[0][ob][r];
-
-    // ---- the sample's reverse sweep (smooth activations): r2 = 2y W3', q2 = r2 . act''(a2) . a2., r1 = (r2 . act'(a2)) W2' ----------------
-    f32x16 r1[1][4];   // r1, then m1 = r1 . a1.
-    zero_acc(r1);
-    if constexpr (kSmooth) {
-        // act''(a2) . a2.: sin -sin(a2) a2.;  tanh -2 h (1 - h^2) a2.
-#pragma unroll
-        for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if constexpr (kSin) t2[0][fb][r] = -a2[0][fb][r] * t2[0][fb][r];
-                else t2[0][fb][r] = -2.0f * a2[0][fb][r] * dact2(fb, r, t2[0][fb][r]);
-            }
-        f32x16 y[1][2];
-        zero_acc(y);
-        mfma_chain<OffW3F, 64, 2, 2, 1>(y, ring2, c.w3f, [&](int st, int) { return a2[0][st >> 4][st & 15]; });
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[0][ob][r] = y[0][ob][r] + y[0][ob][r];
-        f32x16 r2[1][4];
-        zero_acc(r2);
-        mfma_chain<OffW3B, 32, 4, 2, 1>(r2, ring4, c.w3b, [&](int st, int) { return y[0][st >> 4][st & 15]; });
-#pragma unroll
-        for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t2[0][fb][r] = t2[0][fb][r] * r2[0][fb][r];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r2[0][fb][r] = dact2(fb, r, r2[0][fb][r]);
-        mfma_chain<OffW2B, 64, 4, 2, 1>(r1, ring4, c.w2b, [&](int st, int) { return r2[0][st >> 4][st & 15]; });
-        // m1 = r1 . a1. (a1. = W1[j,:] once more; h2. in t1 is dead)
-        zero_acc(t1);
-        mfma_chain<OffW1F, N / 2, 4, 2, 1>(t1, ring4, c.w1f, getej);
-#pragma unroll
-        for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r1[0][fb][r] = r1[0][fb][r] * t1[0][fb][r];
-    }
-
-    // ---- tangent, reverse: r2. = 2 y. W3', d2. = r2. . act'(a2) + q2, r1. = d2. W2' ---------------------------------------------------------
-    f32x16 u2[1][4];
-    zero_acc(u2);
-    mfma_chain<OffW3B, 32, 4, 2, 1>(u2, ring4, c.w3b, [&](int st, int) { return yd[0][st >> 4][st & 15]; });
-#pragma unroll
-    for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (kSmooth) u2[0][fb][r] = dact2(fb, r, u2[0][fb][r]) + t2[0][fb][r];
-            else u2[0][fb][r] = dact2(fb, r, u2[0][fb][r]);
-        }
-    f32x16 u1[1][4];
-    zero_acc(u1);
-    mfma_chain<OffW2B, 64, 4, 2, 1>(u1, ring4, c.w2b, [&](int st, int) { return u2[0][st >> 4][st & 15]; });
-
-    // ---- d1. = r1. . act'(a1) + act''(a1) . m1 and the last product H_z[:,j] = d1. W1' on the VALU, as backward 1 of mlp_value_grad ---------
-    // layer 1 once more for act'(a1), act''(a1) (n / 2 x 4 MFMAs)
-    zero_acc(a1);
-    mfma_chain<OffW1F, N / 2, 4, 2, 1>(a1, ring4, c.w1f, getz);
-    if constexpr (kSmooth) {   // d1. in place of r1., in a pass of its own (three quantities; the products below then read one)
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                float dv;
-                if constexpr (kSin) {
-                    float sn, cs;
-                    sincos1(a1[0][kb][s], sn, cs);
-                    dv = cs * u1[0][kb][s] - sn * r1[0][kb][s];                       // act'' = -sin
-                } else {
-                    const float hh = tanh1(a1[0][kb][s]);
-                    dv = dact1<ACT>(hh, u1[0][kb][s] - 2.0f * hh * r1[0][kb][s]);      // act'' = -2 h act'
-                }
-                fence(dv);
-                u1[0][kb][s] = dv;
-            }
-    }
-    f32x2 part[NP / 2];
-#pragma unroll
-    for (int k = 0; k < NP / 2; ++k) part[k] = f32x2{0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            float dv;
-            if constexpr (kSmooth) dv = u1[0][kb][s];
-            else dv = dact1<ACT>(a1[0][kb][s], u1[0][kb][s]);
-            const f32x2 dv2{dv, dv};
-#pragma unroll
-            for (int q = 0; q < NP / 4; ++q) {
-                const float4 w = c.w1t[(32 * kb + perm(s)) * (NP / 4) + q];
-                part[2 * q + 0] = __builtin_elementwise_fma(f32x2{w.x, w.y}, dv2, part[2 * q + 0]);
-                part[2 * q + 1] = __builtin_elementwise_fma(f32x2{w.z, w.w}, dv2, part[2 * q + 1]);
-            }
-        }
-    // (j as the tile loop's code sees it here and now: the n diagonal terms [k == j] 2 eps_s are per-lane loop invariants otherwise, hoisted
-    //  out of the tile loop and kept in registers through every chain)
-    int jd = j;
-    asm volatile("" : "+v"(jd));
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const float pk = part[k >> 1][k & 1];
-        const float v = pk + __shfl_xor(pk, 32, 64);
-        Hcol[k] = v * p.istd[k] * sj + (k == jd ? 2.f * p.eps_s : 0.f);
-    }
-}
 
 // H (B,n,n) and dy_dx (B,n,64) for a batch of states.  Tile group g = the samples g C .. g C + C - 1; work distribution and LDS staging as in
 // k_value_grad_mfma (a contiguous range of groups per workgroup, pulled by its waves from an LDS counter).

@@ -1,7 +1,8 @@
 """Helpers for inspecting a trained value function (reference utils/debug_helper.py): local minima of V by (damped) Newton steps, the
 locally equivalent linear map of a ReLU network, and two LQR sanity checks.  The two network helpers run batched on the device: V and dV/dx
 come from the fused value-gradient kernel, d2V/dx2 and dy/de from hjbx_value_hessian_f32 (controllers that do not use the fused kernels, e.g.
-float64 ones, go through the torch closed forms of ValueFunctionApproximator); the LQR checks are NumPy."""
+float64 ones, go through the torch closed forms of ValueFunctionApproximator); the LQR checks are NumPy.  local_optimal_x also takes a
+controller with the soft-PD network (hjbx_softpd_value_hessian_f32); the equivalent linear map is for the bias-free PD network only."""
 from typing import Tuple
 
 import numpy as np
@@ -20,9 +21,7 @@ def _restore(t: torch.Tensor, like, one: bool, kind: str):
 
 
 def _value_grad_hessian(nn_policy, x: torch.Tensor):
-    vf = nn_policy.value_function_approximator
-    if getattr(nn_policy, "value_structure", "pd") != "pd":
-        raise NotImplementedError("local_optimal_x exists for the PD value network only (value_structure='pd')")
+    vf = nn_policy.value_function_approximator       # either head: both modules have fused_value_grad / value_and_grad
     if nn_policy.fused_value_grad and x.dtype == torch.float32:
         V, g = vf.fused_value_grad(x)
     else:
@@ -65,6 +64,8 @@ def get_equivalent_matrix_multiplication_for_fully_connected_nn(x, value_functio
     and e = wrap(x - xf) the error coordinates.  x: (n,) or (B, n); W: (n, h3) or (B, n, h3), b: (h3,) or (B, h3).  W = dy/de from the Hessian
     kernel; the network has no biases, so y = W'(e - mean) exactly: b = -W' mean."""
     vf = value_function_approximator
+    if not hasattr(vf, "weights"):
+        raise ValueError("the equivalent linear map exists for the bias-free PD network, not for the soft-PD network (biases, scalar head)")
     if vf.activation != "relu":
         raise ValueError(f"the equivalent linear map exists for a ReLU network, this one uses {vf.activation!r}")
     dtype = vf.weights[0].dtype

@@ -11,7 +11,11 @@ ratios of tests/test_gpu_value_hessian.py sit under "parity" in the same file) a
   columns of a tile are NOT counted, so the fraction below is that of useful work), that over the 157.3 TFLOP/s float32 MFMA peak, and the
   speed-up over the torch form.
 
-    python tools/bench_value_hessian.py [--batch 131072] [--reps 10] [--inner 20] [--warmup 2] [--buffers 4]
+    python tools/bench_value_hessian.py [--batch 131072] [--reps 10] [--inner 20] [--warmup 2] [--buffers 4] [--head pd|soft_pd]
+
+--head soft_pd times hjbx_softpd_value_hessian_f32 (the soft-PD network of the notebooks, biases seeded uniform(-0.5, 0.5)) next to
+SoftPDValueFunctionApproximator.value_hessian in float32 for tanh and sin, and writes profiles/softpd_value_hessian.json instead; the
+default, pd, is as described above.
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ from q_learning_with_hjb_amd.dynamics.cartpole import Cartpole  # noqa: E402
 from q_learning_with_hjb_amd.dynamics.quadrotors import NearHoverQuadcopter  # noqa: E402
 
 CASES = [("cartpole", "tanh"), ("cartpole", "relu"), ("nearhover", "tanh"), ("nearhover", "relu")]
+SOFT_CASES = [("cartpole", "tanh"), ("cartpole", "sin"), ("nearhover", "tanh"), ("nearhover", "sin")]
 PEAK_F32_MFMA = 157.3e12
 
 
@@ -42,12 +47,18 @@ def flop_per_state(n, activation):
     return n * (layer1 + wide + narrow + 2 * 128 * n)
 
 
-def make(name, activation):
+def make(name, activation, head="pd"):
     if name == "cartpole":
         d, cfg = Cartpole(D.cartpole_dynamics_config()), D.cartpole_vhjb_config()
     else:
         d, cfg = NearHoverQuadcopter(D.near_hover_dynamics_config()), D.near_hover_vhjb_config()
-    ctl = VHJBController(d, cfg, activation=activation, graph_updates=False)     # lecun-normal weights from the config's seed
+    ctl = VHJBController(d, cfg, activation=activation, graph_updates=False, value_structure=head)     # lecun-normal weights from the config's seed
+    if head == "soft_pd":
+        gen = torch.Generator().manual_seed(0)
+        with torch.no_grad():
+            for p in ctl.value_function_approximator.parameters():
+                if p.dim() == 1:
+                    p.copy_(torch.rand(p.shape, generator=gen) - 0.5)
     return d, ctl
 
 
@@ -78,13 +89,17 @@ def main():
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--buffers", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "value_hessian.json"))
+    ap.add_argument("--head", choices=("pd", "soft_pd"), default="pd")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    soft = args.head == "soft_pd"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "softpd_value_hessian.json" if soft else "value_hessian.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_value_hessian: needs an MI355X (there is no CPU path to time)")
     res = {}
-    for name, act in CASES:
-        d, ctl = make(name, act)
+    for name, act in (SOFT_CASES if soft else CASES):
+        d, ctl = make(name, act, args.head)
         vf = ctl.value_function_approximator
         n = d.state_dim
         rng = np.random.default_rng(0)
@@ -97,7 +112,8 @@ def main():
         del Hk, Ht, scale
         k_ms, k_lo, k_hi = median_ms(vf.fused_value_hessian, xs, args.warmup, args.reps, args.inner)
         t_ms, t_lo, t_hi = median_ms(vf.value_hessian, xs, args.warmup, args.reps, max(1, args.inner // 10))
-        flop = flop_per_state(n, act)
+        # soft-PD: the formulation's own count, ten chains per column (the last product on the VALU is not counted)
+        flop = 8 * n * (128 * n + 128 * 128 + 128 * 64) if soft else flop_per_state(n, act)
         res[f"{name}_{act}"] = dict(n=n, kernel_ms=round(k_ms, 4), kernel_ms_min_max=[round(k_lo, 4), round(k_hi, 4)],
                                     states_per_s=round(args.batch / (k_ms * 1e-3), 1), flop_per_state=flop,
                                     fraction_of_f32_mfma_peak=round(flop * args.batch / (k_ms * 1e-3) / PEAK_F32_MFMA, 4),
@@ -105,7 +121,7 @@ def main():
                                     speedup_over_torch=round(t_ms / k_ms, 2), max_kernel_vs_torch_rel=agree)
         del ctl, xs
         torch.cuda.empty_cache()
-    timing = dict(tool="bench_value_hessian", B=args.batch, reps=args.reps, inner=args.inner, warmup=args.warmup, buffers=args.buffers,
+    timing = dict(tool="bench_value_hessian" + (" --head soft_pd" if soft else ""), B=args.batch, reps=args.reps, inner=args.inner, warmup=args.warmup, buffers=args.buffers,
                   device=torch.cuda.get_device_name(0), peak_f32_mfma_flops=PEAK_F32_MFMA, cases=res)
     old = {}
     if os.path.exists(args.out):
