@@ -361,7 +361,7 @@ def softpd_value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
 def softpd_value_hessian(sys, mlp_desc, x):
     """hjbx_softpd_value_hessian_f32: H (B, n, n) = d2V/dx2 of the soft-PD value network (mlp_desc: _abi.HjbxSoftpdMlp) on the matrix cores
     (f32 only; relu: zeros).  ValueError for a wrong shape or dtype, NotImplementedError for what the library refuses (a user-defined
-    system, a (system, activation) pair it does not ship)."""
+    system, a linear system with n outside {2, 4, 6})."""
     B = x.shape[0]
     if x.dtype != torch.float32:
         raise ValueError(f"x has dtype {x.dtype}, expected {torch.float32}")

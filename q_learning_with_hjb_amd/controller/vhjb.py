@@ -319,7 +319,8 @@ class SoftPDValueFunctionApproximator(torch.nn.Module):
     @torch.no_grad()
     def fused_value_hessian(self, x: torch.Tensor) -> torch.Tensor:
         """d2V/dx2 (B, n, n) from the matrix-core kernel hjbx_softpd_value_hessian_f32 (float32; columns are computed one by one, so H is
-        symmetric up to rounding only; relu: zeros).  NotImplementedError for what the library refuses."""
+        symmetric up to rounding only; relu: zeros).  NotImplementedError for what the library refuses (a user-defined system, a linear
+        system with n outside {2, 4, 6})."""
         for w in self.layers:
             assert w.is_contiguous() and w.dtype == torch.float32
         return _ops.softpd_value_hessian(self.dynamics.system, self.descriptor(), x)
@@ -673,14 +674,14 @@ class VHJBController(Controller):
     @torch.no_grad()
     def value_hessian(self, x: torch.Tensor) -> torch.Tensor:
         """d2V/dx2 (B, n, n) for a (B, n) device batch, for either value network: the matrix-core kernel where this controller runs the fused
-        value network, the torch closed form of the module's value_hessian otherwise -- and for a soft-PD (system, activation) pair the
-        library refuses."""
+        value network, the torch closed form of the module's value_hessian otherwise -- and for a soft-PD network on a system the library has
+        no kernel for (a linear system with n outside {2, 4, 6})."""
         vf = self.value_function_approximator
         if self.fused_value_grad and x.dtype == torch.float32 and self.dynamics.system.kind != _abi.SYS_USER:
             try:
                 return vf.fused_value_hessian(x)
             except NotImplementedError:
-                if self.value_structure != "soft_pd":      # (the PD unit ships every pair: nothing to fall back from)
+                if self.value_structure != "soft_pd":      # (only the soft-PD network falls back: a refusal for the PD network is the caller's to see)
                     raise
         return vf.value_hessian(x)
 

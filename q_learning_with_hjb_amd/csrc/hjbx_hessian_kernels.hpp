@@ -1,13 +1,15 @@
-// hjbx_hessian_kernels.hpp -- device code shared by the two Hessian units (hjbx_hessian.hip: PD value network; hjbx_softpd_hessian.hip:
-// soft-PD network of the notebooks): one column of a tile, i.e. its sample's forward and reverse sweep and the tangent sweep along its
-// direction, on the five chains of the value gradient.  Design and register budget: top of hjbx_hessian.hip.  Each unit instantiates its own
-// head (SOFT), the way mlp_value_grad<S, TL, ACT, SOFT> serves hjbx_mlp.hip and hjbx_softpd.hip.
+// hjbx_hessian_kernels.hpp -- the device code of the two Hessian units (hjbx_hessian.hip: PD value network; hjbx_softpd_hessian.hip: soft-PD
+// network of the notebooks): mlp_value_hessian, one column of a tile, i.e. its sample's forward and reverse sweep and the tangent sweep along
+// its direction on the five chains of the value gradient, and k_value_hessian, the persistent kernel around it, templated on the network's
+// head like the kernels of hjbx_mlp_kernels.hpp.  Design and register budget: top of hjbx_hessian.hip; launcher, dispatcher and checks:
+// hjbx_mlp_host.hpp.  Each unit instantiates only its own head.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "hjbx_internal.hpp"
 #include "hjbx_systems.hpp"
 #include "hjbx_mlp_core.hpp"
+#include "hjbx_mlp_kernels.hpp"   // the heads: MlpHeadPd, MlpHeadSoft
 
 using namespace hjbx;
 
@@ -276,5 +278,66 @@ __device__ __forceinline__ void mlp_value_hessian(const S& sys, const MlpP<S::N>
             const float v = pk + __shfl_xor(pk, 32, 64);
             Hcol[k] = v * p.istd[k] * sj + (k == jd ? 2.f * p.eps_s : 0.f);
         }
+    }
+}
+
+// ---- the kernel: H (B,n,n) and, PD head only, dy_dx (B,n,64) for a batch of states (hjbx_value_hessian_f32, hjbx_softpd_value_hessian_f32) ----
+// Tile group g = the samples g C .. g C + C - 1; work distribution and LDS staging as in k_value_grad_mfma (a contiguous range of groups per
+// workgroup, pulled by its waves from an LDS counter).  The soft-PD head has H as its one output: it takes Hout as given and ignores dyout.
+static constexpr int kHessWaves = 4;   // one wave per SIMD: up to 512 registers each
+
+template <typename S, int WAVES, int ACT, typename HEAD>
+__global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_value_hessian(S sys, MlpP<S::N> p, const float* __restrict__ W1g,
+                                                                       const float* __restrict__ W2g, const float* __restrict__ W3g,
+                                                                       const float* __restrict__ x, float* __restrict__ Hout,
+                                                                       float* __restrict__ dyout, int64_t B, int64_t ngroups, HEAD head) {
+    constexpr int N = S::N;
+    constexpr int C = 32 / N;   // samples per tile
+    static_assert(N % 2 == 0 && C >= 1, "state dimension must be even (k-steps of 2) and at most 32");
+    __shared__ __attribute__((aligned(256))) typename HEAD::template Lds<N, 0> L;
+    const int tid = threadIdx.x;
+    if (tid == 0) L.next = WAVES;  // groups 0..WAVES-1 of the range are taken statically
+    mlp_fill_lds<N, WAVES * 64>(L, W1g, W2g, W3g, tid);
+    if constexpr (HEAD::kSoft) mlp_fill_bias<WAVES * 64>(L.bias, head.b1, head.b2, head.b3, head.w4, head.b4, tid);
+    __syncthreads();
+    // (the wave index through readfirstlane: the tile group then lives in SGPRs, see k_vhjb_rollout_mfma)
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const auto c = [&] { return mlp_ctx<N>(L, lane); }();
+    const int i = c.i, h = c.h;
+    const bool busy = i < C * N;             // an idle column computes on the target state and stores nothing
+    const int cs = busy ? i / N : 0;         // sample of the tile
+    const int j = busy ? i - cs * N : 0;     // direction
+    float sj = p.istd[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) sj = (j == k) ? p.istd[k] : sj;
+
+    const int64_t groups_per_wg = (ngroups + gridDim.x - 1) / gridDim.x;
+    const int64_t g_begin = (int64_t)blockIdx.x * groups_per_wg;
+    const int64_t g_end = (g_begin + groups_per_wg < ngroups) ? g_begin + groups_per_wg : ngroups;
+
+    // No prefetch of the next tile's rows, unlike k_value_grad_mfma: a tile is ~1600 MFMAs (40 us), the exposed load a few per cent of it,
+    // and n more registers held through every chain are what the sin instantiation for n = 10 has not got.
+    for (int64_t grp = g_begin + wave; grp < g_end;) {
+        // the weights are loop invariant: without this barrier LICM hoists LDS reads out of the tile loop
+        asm volatile("" ::: "memory");
+        const int64_t env = grp * C + cs;
+        const bool live = busy && env < B;
+        float xs[N], Hcol[N];
+        load_sample<N>(x, p, env, live, xs);
+        bool want_h = true;   // soft-PD: no run-time test of either output pointer
+        if constexpr (HEAD::kSoft) {
+            mlp_value_hessian<S, ACT, true>(sys, p, c, xs, j, sj, true, nullptr, Hcol, &L.bias);
+        } else {
+            want_h = Hout != nullptr;
+            float* dyp = (dyout && live) ? dyout + (env * N + j) * kH3 + 4 * h : nullptr;
+            mlp_value_hessian<S, ACT>(sys, p, c, xs, j, sj, want_h, dyp, Hcol);
+        }
+        if (want_h && live && h == 0) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) Hout[(env * N + k) * N + j] = Hcol[k];
+        }
+        int nxt = 0;
+        if (lane == 0) nxt = atomicAdd(&L.next, 1);
+        grp = g_begin + __builtin_amdgcn_readfirstlane(nxt);
     }
 }

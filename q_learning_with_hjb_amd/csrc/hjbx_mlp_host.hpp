@@ -1,5 +1,6 @@
 // hjbx_mlp_host.hpp -- the one host path between a C entry point and a launch of the value network's matrix-core kernels (hjbx_mlp.hip,
-// hjbx_softpd.hip, hjbx_train.hip, hjbx_train_coop.hip, and hjbx_user.hip for a user-defined system): the network of either head as one
+// hjbx_softpd.hip, hjbx_hessian.hip, hjbx_softpd_hessian.hip, hjbx_train.hip, hjbx_train_coop.hip, and hjbx_user.hip for a user-defined
+// system): the network of either head as one
 // descriptor (hjbx_net), the argument checks of the entry points, the normalisation constants as the kernels take them, the persistent
 // grids, and -- templated on the head -- one launcher and one system dispatcher per kernel.  Not part of the ABI.
 #pragma once
@@ -7,6 +8,7 @@
 
 #include "hjbx_host.hpp"
 #include "hjbx_mlp_kernels.hpp"
+#include "hjbx_hessian_kernels.hpp"
 
 // ---- the network descriptor --------------------------------------------------------------------------------------------------------
 inline hjbx_net make_net(const hjbx_mlp* mlp) {
@@ -34,7 +36,7 @@ template <typename Head> inline Head make_head(const hjbx_net& net) {
 
 // ---- argument checks ---------------------------------------------------------------------------------------------------------------
 // The order of the checks is that of the PD entry points (hjbx_value_grad_f32, hjbx_vhjb_rollout_f32); the messages are each head's own.
-static constexpr int kEmptyCall = 1;   // returned by the two entry-point checks for a call with nothing to compute: the caller returns HJBX_OK
+static constexpr int kEmptyCall = 1;   // returned by the entry-point checks for a call with nothing to compute: the caller returns HJBX_OK
 
 inline int check_features(const char* who, const hjbx_net& net) {
     if (net.h1 != kH1 || net.h2 != kH2 || net.h3 != kH3)
@@ -73,6 +75,22 @@ inline int check_value_grad(const char* who, const hjbx_system* sys, const hjbx_
     return check_std(who, net, sys->n);
 }
 
+// hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32 after their NULL-descriptor check: the checks of check_value_grad in its order, for
+// these entry points' outputs (dy = dy_dx, PD head only: the soft-PD entry point passes NULL); no kernel exists for a user-defined system
+inline int check_value_hessian(const char* who, const hjbx_system* sys, const hjbx_net& net, const float* x, const float* H, const float* dy, int64_t B) {
+    if (B < 0) return hjbx_set_error(HJBX_EINVAL, "%s: negative batch size", who);
+    if (B == 0 || (!H && !dy)) return kEmptyCall;
+    if (!x || !net.W1 || !net.W2 || !net.W3 || (net.soft && (!net.b1 || !net.b2 || !net.b3 || !net.w4 || !net.b4)))
+        return hjbx_set_error(HJBX_EINVAL, net.soft ? "%s: NULL x, weight or bias pointer" : "%s: NULL x or weight pointer", who);
+    if (sys->kind == HJBX_SYS_USER)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: user-defined systems are not supported, the kernel exists for the built-in systems only", who);
+    if (int rc = check_features(who, net)) return rc;
+    if (!state_rows_aligned(x, sys) || (reinterpret_cast<uintptr_t>(H) & 15u) || (reinterpret_cast<uintptr_t>(dy) & 15u))
+        return hjbx_set_error(HJBX_EINVAL, net.soft ? "%s: x must be aligned to its row vector width, H to 16 bytes"
+                                                    : "%s: x must be aligned to its row vector width, H and dy_dx to 16 bytes", who);
+    return check_std(who, net, sys->n);
+}
+
 // hjbx_vhjb_rollout_f32 / hjbx_softpd_rollout_f32 after their NULL-descriptor check
 inline int check_rollout(const char* who, const hjbx_system* sys, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& a) {
     if (int rc = check_task(task)) return rc;
@@ -91,19 +109,20 @@ inline int check_rollout(const char* who, const hjbx_system* sys, const hjbx_tas
 }
 
 // ---- grids -------------------------------------------------------------------------------------------------------------------------
-// value gradient: tile groups of 32 * TL environments; one resident workgroup per CU (106 KB of LDS each); small batches are spread one
-// tile group per CU rather than packed eight to a workgroup, so up to n_cu matrix pipes work on them
-inline int mlp_value_grad_grid(int64_t B, int TL, int64_t* ngroups, int64_t* grid, const char* who) {
-    *ngroups = (B + 32 * TL - 1) / (32 * TL);
+// tile groups of `per_group` samples (value gradient: 32 * TL environments; Hessian: 32 / n samples, n columns each); one resident workgroup
+// per CU (106 KB of LDS each); small batches are spread one tile group per CU rather than packed eight to a workgroup, so up to n_cu matrix
+// pipes work on them
+inline int mlp_persistent_grid(int64_t B, int per_group, int64_t* ngroups, int64_t* grid, const char* who) {
+    *ngroups = (B + per_group - 1) / per_group;
     const int n_cu = hjbx_device_cus();
     if (n_cu <= 0) return hjbx_set_error(HJBX_ENODEVICE, "%s: no HIP device", who);
     *grid = *ngroups < n_cu ? *ngroups : n_cu;
     return HJBX_OK;
 }
 
-// rollout: as above with one tile per wave, plus the schedule and the test hook for workgroups that cannot be resident before others finish
+// rollout: as above with one tile of 32 environments per wave, plus the schedule and the test hook for workgroups that cannot be resident before others finish
 inline int mlp_rollout_grid(int64_t B, int64_t* ngroups, int64_t* grid, int* sched, const char* who) {
-    if (int rc = mlp_value_grad_grid(B, 1, ngroups, grid, who)) return rc;
+    if (int rc = mlp_persistent_grid(B, 32, ngroups, grid, who)) return rc;
     *sched = hjbx_option_value(HJBX_OPT_ROLLOUT_SCHEDULE);
     *grid += hjbx_option_value(HJBX_OPT_ROLLOUT_EXTRA_WORKGROUPS);
     if (*grid > kMaxGrid) *grid = kMaxGrid;
@@ -117,9 +136,22 @@ template <typename S, int TL, int WAVES, int ACT, int ARITH, typename Head>
 int launch_value_grad(S sys, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* st, const char* who) {
     const MlpP<S::N> p = make_mlp_params<S::N>(net);
     int64_t ngroups = 0, grid = 0;
-    if (int rc = mlp_value_grad_grid(B, TL, &ngroups, &grid, who)) return rc;
+    if (int rc = mlp_persistent_grid(B, 32 * TL, &ngroups, &grid, who)) return rc;
     hipLaunchKernelGGL((k_value_grad_mfma<S, TL, WAVES, ACT, ARITH, Head>), dim3((unsigned)grid), dim3(WAVES * 64), 0, (hipStream_t)st, sys, p, net.W1,
                        net.W2, net.W3, x, V, g, B, ngroups, make_head<Head>(net));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "%s: %s", who, hipGetErrorString(e));
+    return HJBX_OK;
+}
+
+// Hessian: 32 / n samples per tile, kHessWaves waves per workgroup (design: top of hjbx_hessian.hip); dy = NULL for the soft-PD head
+template <typename S, int ACT, typename Head>
+int launch_value_hessian(S sys, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B, void* st, const char* who) {
+    const MlpP<S::N> p = make_mlp_params<S::N>(net);
+    int64_t ngroups = 0, grid = 0;
+    if (int rc = mlp_persistent_grid(B, 32 / S::N, &ngroups, &grid, who)) return rc;
+    hipLaunchKernelGGL((k_value_hessian<S, kHessWaves, ACT, Head>), dim3((unsigned)grid), dim3(kHessWaves * 64), 0, (hipStream_t)st, sys, p, net.W1,
+                       net.W2, net.W3, x, H, dy, B, ngroups, make_head<Head>(net));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "%s: %s", who, hipGetErrorString(e));
     return HJBX_OK;
@@ -150,11 +182,10 @@ int launch_rollout(const hjbx_system* sysh, S sys, const hjbx_task* task, const 
 
 // ---- system kind -> instantiation --------------------------------------------------------------------------------------------------
 // Development builds (-DHJBX_MLP_DEV: 30 instantiations take a minute per variant) narrow the two lists below to the cart-pole, with
-// -DHJBX_MLP_DEV_QUAD2D the planar quadrotor's value gradient as well; what they keep is launched as in the product.
-// Value gradient: seven cases (V does not depend on m; wrap is all the kernel takes from the system, so its parameters stay unset).
-template <int TL, int WAVES, int ACT, int ARITH, typename Head>
-int dispatch_value_grad(const hjbx_system* sys, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* st, const char* who) {
-    auto go = [&](auto s) { return launch_value_grad<decltype(s), TL, WAVES, ACT, ARITH, Head>(s, net, x, V, g, B, st, who); };
+// -DHJBX_MLP_DEV_QUAD2D the planar quadrotor's value gradient (and with it the Hessian) as well; what they keep is launched as in the product.
+// Value gradient and Hessian: seven cases (V does not depend on m; wrap is all the kernels take from the system, so its parameters stay
+// unset).  go(system) launches one instantiation.
+template <typename Go> int dispatch_value_system(const hjbx_system* sys, const char* who, Go go) {
     switch (sys->kind) {
     case HJBX_SYS_CARTPOLE: return go(Cartpole<float>{});
 #if !defined(HJBX_MLP_DEV) || defined(HJBX_MLP_DEV_QUAD2D)
@@ -171,6 +202,14 @@ int dispatch_value_grad(const hjbx_system* sys, const hjbx_net& net, const float
 #endif
     }
     return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no kernel for system kind %d with n=%d", who, sys->kind, sys->n);
+}
+template <int TL, int WAVES, int ACT, int ARITH, typename Head>
+int dispatch_value_grad(const hjbx_system* sys, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* st, const char* who) {
+    return dispatch_value_system(sys, who, [&](auto s) { return launch_value_grad<decltype(s), TL, WAVES, ACT, ARITH, Head>(s, net, x, V, g, B, st, who); });
+}
+template <int ACT, typename Head>
+int dispatch_value_hessian(const hjbx_system* sys, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B, void* st, const char* who) {
+    return dispatch_value_system(sys, who, [&](auto s) { return launch_value_hessian<decltype(s), ACT, Head>(s, net, x, H, dy, B, st, who); });
 }
 
 // Rollout: every built-in system of even state dimension (with_system), each with the integrators it has.
@@ -193,8 +232,10 @@ int dispatch_rollout(const hjbx_system* sys, const hjbx_task* task, const hjbx_n
 // ---- the hidden per-object symbols -------------------------------------------------------------------------------------------------
 // hjbx_mlp.hip and hjbx_softpd.hip are compiled once per variant; object v defines <prefix>_value_grad_act<v> and <prefix>_rollout_act<v>
 // (the two dispatchers above for its activation and arithmetic), and the object with the C entry points calls the one it selects.
+// hjbx_hessian.hip and hjbx_softpd_hessian.hip do the same with <prefix>_value_hessian_act<v>, v = hjbx_activation.
 using mlp_value_grad_fn = int(const hjbx_system* sys, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who);
 using mlp_rollout_fn = int(const hjbx_system* sys, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& a, const char* who);
+using mlp_value_hessian_fn = int(const hjbx_system* sys, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B, void* stream, const char* who);
 #define HJBX_MLP_SYM2(prefix, name, v) prefix##name##v
 #define HJBX_MLP_SYM(prefix, name, v) HJBX_MLP_SYM2(prefix, name, v)
 #define HJBX_MLP_DECLARE_VARIANT(prefix, v)                                                          \
@@ -208,4 +249,10 @@ using mlp_rollout_fn = int(const hjbx_system* sys, const hjbx_task* task, const 
     int HJBX_MLP_SYM(prefix, _rollout_act, v)(const hjbx_system* sys, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& a,       \
                                               const char* who) {                                                                                   \
         return dispatch_rollout<WAVES, ACT, ARITH, Head>(sys, task, net, a, who);                                                                  \
+    }
+#define HJBX_HESS_DECLARE_VARIANT(prefix, v) __attribute__((visibility("hidden"))) mlp_value_hessian_fn HJBX_MLP_SYM(prefix, _value_hessian_act, v);
+#define HJBX_HESS_DEFINE_VARIANT(prefix, v, ACT, Head)                                                                                              \
+    int HJBX_MLP_SYM(prefix, _value_hessian_act, v)(const hjbx_system* sys, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B,    \
+                                                    void* stream, const char* who) {                                                               \
+        return dispatch_value_hessian<ACT, Head>(sys, net, x, H, dy, B, stream, who);                                                              \
     }

@@ -457,7 +457,7 @@ int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float*
         auto blob = user_blob<float>(s);
         MlpP<N> p = make_mlp_params<N>(net);
         int64_t ngroups = 0, grid = 0;
-        if (int rc = mlp_value_grad_grid(B, 1, &ngroups, &grid, who)) return rc;
+        if (int rc = mlp_persistent_grid(B, 32, &ngroups, &grid, who)) return rc;
         MlpHeadSoft soft = make_head<MlpHeadSoft>(net);
         MlpHeadPd pd{};
         void* a[] = {&blob, &p, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&x, (void*)&V, (void*)&g, (void*)&B, &ngroups,

@@ -8,25 +8,9 @@ same statements evaluated in float32 on the CPU (the "CPU float build" yardstick
     H_z = A3 diag(w4 . act''(a3)) A3' + A2 diag(r2 . act''(a2)) A2' + A1 diag(r1 . act''(a1)) A1'
     H_x = H_z / (std std')                                                     (no eps term; the wrap is data: d wrap = I)
 """
-import os
-import re
-
 import numpy as np
 
 from hessref import _ACT
-
-SYSTEM_TAGS = ("cartpole", "quad2d", "linear2", "linear4", "linear6", "acrobot", "nearhover")
-
-
-def shipped_pairs():
-    """The (system tag, hjbx_activation) pairs hjbx_softpd_value_hessian_f32 has kernels for, read from the table the dispatcher itself is
-    made from (HJBX_SOFTPD_HESS_SHIPPED in csrc/hjbx_softpd_hessian.hip); relu needs none (H = 0)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "q_learning_with_hjb_amd", "csrc", "hjbx_softpd_hessian.hip")).read()
-    body = re.search(r"#define HJBX_SOFTPD_HESS_SHIPPED\(X\)((?:.*\\\n)*.*)\n", src).group(1)
-    pairs = [(s, int(a)) for s, a in re.findall(r"X\((\w+),\s*(\d)\)", body)]
-    assert pairs and len(set(pairs)) == len(pairs) and all(s in SYSTEM_TAGS and a in (1, 2) for s, a in pairs), pairs
-    return pairs
 
 
 class SoftHessRef:

@@ -20,7 +20,7 @@ import torch
 
 from conftest import ANGLE_IDX, ROOT, make_dynamics, make_vhjb_config
 from oracle import oracle as O
-from softhessref import SoftHessRef, shipped_pairs
+from softhessref import SoftHessRef
 from q_learning_with_hjb_amd import _abi, _ops
 from q_learning_with_hjb_amd.controller.vhjb import SoftPDValueFunctionApproximator, VHJBController
 from q_learning_with_hjb_amd.utils.debug_helper import local_optimal_x
@@ -31,8 +31,6 @@ U = 2.0 ** -24
 B_FULL = 1000                                   # not a multiple of any C = 32 // n and not of 32
 SYSTEMS_H = ["linear", "cartpole", "quad2d", "nearhover"]      # n = 2, 4, 6, 10
 ACTS = ["tanh", "sin"]
-TAG = {"linear": "linear2", "cartpole": "cartpole", "quad2d": "quad2d", "nearhover": "nearhover"}
-ACT_CODE = {"tanh": _abi.ACT_TANH, "sin": _abi.ACT_SIN}
 SENTINEL = 12345.678
 EPS_G = 2e-5                                    # the gradient kernel's own parity bound (test_gpu_vhjb.py)
 
@@ -56,19 +54,6 @@ def _write_report():
             json.dump(old, f, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def _shipped(name, activation):
-    return activation == "relu" or (TAG[name], ACT_CODE[activation]) in shipped_pairs()
-
-
-def _refused(c, name, activation):
-    """A pair the table does not ship: the library must refuse it by name (there is then nothing of the kernel to test).  -> refused?"""
-    if _shipped(name, activation):
-        return False
-    with pytest.raises(NotImplementedError, match="no kernel for the pair"):
-        c.vf.fused_value_hessian(c.x)
-    return True
 
 
 def _controller(name, activation, dtype=torch.float32, seed=3):
@@ -170,13 +155,6 @@ def test_hessian_vs_f64_closed_form(name, activation):
     et = _rel_err(Ht.cpu().numpy(), c.H64)[c.keep].max()
     print(f"    {name} {activation}: torch closed form (float32) err / sample scale max {et:.2e}")
     assert et <= 1e-4, et
-    if not _shipped(name, activation):
-        # a pair the library refuses: the refusal names it, and the controller falls back to the closed form
-        with pytest.raises(NotImplementedError, match="no kernel for the pair"):
-            c.vf.fused_value_hessian(c.x)
-        assert torch.equal(c.ctl.value_hessian(c.x), Ht)
-        _report[f"{name}-{activation}"] = dict(refused=True, torch_f32_max=float(et))
-        return
     Hk = c.vf.fused_value_hessian(c.x)
     torch.cuda.synchronize()
     assert Hk.shape == (B_FULL, n, n) and Hk.dtype == torch.float32
@@ -213,8 +191,6 @@ def test_work_distribution_and_tile_edges(name, activation):
     buffer with two more rows: rows >= B keep the sentinel, rows < B equal the large run's bit for bit (a sample's result depends on its own
     state only, not on its place in a tile or on the grid)."""
     base = case(name, activation)
-    if _refused(base, name, activation):
-        return
     n = base.ctl.state_dim
     C = 32 // n
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -236,8 +212,6 @@ def test_work_distribution_and_tile_edges(name, activation):
 # ------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name, activation", [("cartpole", "tanh"), ("nearhover", "sin")])
 def test_exact_identities(name, activation):
-    if _refused(case(name, activation), name, activation):
-        return
     d, ctl = _controller(name, activation)          # a controller of its own: the weights are edited
     vf = ctl.value_function_approximator
     x = case(name, activation).x
