@@ -36,6 +36,7 @@ extern "C" {
 #define HJBX_HAS_REPLAY_APPEND 1 /* hjbx_replay_append_f32 / _f64 exist (added without a version step: an addition, nothing else changed) */
 #define HJBX_HAS_USER_MATRIX_CORES 1 /* hjbx_system_enable_matrix_cores / hjbx_system_matrix_cores / hjbx_system_code_object exist (an addition) */
 #define HJBX_HAS_USER_TRAIN 1 /* hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 take an enabled user-defined system; HJBX_CODE_TRAIN exists (an addition) */
+#define HJBX_HAS_USER_VALUE_HESSIAN 1 /* hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32 take an enabled user-defined system; HJBX_CODE_HESSIAN exists (an addition) */
 #define HJBX_MAX_N 10    /* largest state dimension (NearHoverQuadcopter) */
 #define HJBX_MAX_M 3     /* largest control dimension */
 
@@ -258,11 +259,14 @@ int hjbx_system_matrix_cores(const hjbx_system* sys);
 /* The gfx950 code objects (ELF) a user-defined system runs (dynamics_basic.py:64-94 compiled; vhjb.py:17-60, 162-193, 201-202 for the
  * matrix-core units), for inspection: copies up to `len` bytes into buf (may be NULL) and returns the object's size.  `which` =
  * HJBX_CODE_STREAMING, HJBX_CODE_MATRIX_CORES(head, activation) with head 0 = hjbx_mlp, 1 = hjbx_softpd_mlp, or HJBX_CODE_TRAIN(activation):
- * the parameter-gradient unit of hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 (four kernels) -- compiled now if it has not
- * been yet.  Returns 0 on failure (hjbx_last_error; hjbx_last_compile_log when the compiler refused the source). */
+ * the parameter-gradient unit of hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32 (four kernels), or HJBX_CODE_HESSIAN(head, activation):
+ * the value-Hessian unit of hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32 (one kernel; HJBX_EUNSUPPORTED for head 1 with
+ * HJBX_ACT_RELU: that H is identically zero and has no kernel) -- compiled now if it has not been yet.  Returns 0 on failure
+ * (hjbx_last_error; hjbx_last_compile_log when the compiler refused the source). */
 #define HJBX_CODE_STREAMING 0
 #define HJBX_CODE_MATRIX_CORES(head, activation) (1 + 3 * (head) + (activation))
 #define HJBX_CODE_TRAIN(activation) (7 + (activation))
+#define HJBX_CODE_HESSIAN(head, activation) (10 + 3 * (head) + (activation))
 size_t hjbx_system_code_object(const hjbx_system* sys, int which, void* buf, size_t len);
 /* Dynamics.get_dimension, dynamics_basic.py:31-36 */
 int hjbx_dims(const hjbx_system* sys, int* n, int* m);
@@ -396,7 +400,12 @@ int hjbx_softpd_rollout_f32(const hjbx_system* sys, const hjbx_task* task, const
  * crosses zero.  H is computed column by column (each column is one tangent sweep through the network): it is symmetric up to rounding and
  * NOT bitwise symmetric.  Results are deterministic: two calls on the same input agree bit for bit.
  * Always the float32 MFMA arithmetic (HJBX_OPT_MLP_ARITHMETIC does not apply).  Features [128,128,64]; relu, tanh and sin; the built-in
- * systems hjbx_value_grad_f32 dispatches.  A user-defined system (HJBX_SYS_USER) returns HJBX_EUNSUPPORTED.  No workspace.
+ * systems hjbx_value_grad_f32 dispatches, and a user-defined system (HJBX_SYS_USER) whose handle asked for the matrix-core kernels
+ * (hjbx_system_enable_matrix_cores): the first call for an activation compiles the same kernel for the user's struct
+ * (csrc/hjbx_user_hessian_kernels.hpp: hiprtc, seconds, once per handle; HJBX_CODE_HESSIAN(0, activation) returns the code object).  A
+ * kernel that would need scratch is never launched: HJBX_EUNSUPPORTED, the refusal is remembered and the handle keeps its other kernels;
+ * HJBX_EINVAL + hjbx_last_compile_log when the source does not compile there.  A user-defined system that has not asked returns
+ * HJBX_EUNSUPPORTED.  No workspace.
  * x must be aligned to its row vector width, H and dy_dx to 16 bytes.  B == 0 or both outputs NULL: HJBX_OK, nothing is launched. */
 #define HJBX_HAS_VALUE_HESSIAN 1 /* the entry point below exists (an addition, nothing else changed) */
 int hjbx_value_hessian_f32(const hjbx_system* sys, const hjbx_mlp* mlp, const float* x, float* H /* (B,n,n) or NULL */,
@@ -416,7 +425,10 @@ int hjbx_value_hessian_f32(const hjbx_system* sys, const hjbx_mlp* mlp, const fl
  * agree bit for bit.  ReLU has act'' = 0, so the scalar piecewise-linear network has H = 0 wherever it is defined: there is no ReLU kernel,
  * the entry point fills H with zeros on the stream.  tanh and sin run on the matrix cores (float32 MFMA; HJBX_OPT_MLP_ARITHMETIC does not
  * apply) for the built-in systems hjbx_softpd_value_grad_f32 dispatches; a (system, activation) pair whose kernel would need scratch is
- * refused with HJBX_EUNSUPPORTED and a message that names it (none at present).  A user-defined system returns HJBX_EUNSUPPORTED.
+ * refused with HJBX_EUNSUPPORTED and a message that names it (none at present).  A user-defined system whose handle asked for the
+ * matrix-core kernels (hjbx_system_enable_matrix_cores) runs the same kernel, compiled for its struct at the first call for an activation
+ * (HJBX_CODE_HESSIAN(1, activation); scratch and compile failures as for hjbx_value_hessian_f32; relu compiles nothing, H is zero-filled);
+ * one that has not asked returns HJBX_EUNSUPPORTED.
  * Features [128,128,64].  No workspace.  x must be aligned to its row vector width, H to 16 bytes.  B == 0 or H == NULL: HJBX_OK, nothing
  * is launched. */
 #define HJBX_HAS_SOFTPD_VALUE_HESSIAN 1 /* the entry point below exists (an addition, nothing else changed) */

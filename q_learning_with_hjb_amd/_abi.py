@@ -30,6 +30,7 @@ OPT_ROLLOUT_SCHEDULE, OPT_ROLLOUT_EXTRA_WORKGROUPS, OPT_STREAM_ROWS, OPT_MLP_ARI
 OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE = 0, -1, -2, -3, -4
 CODE_STREAMING = 0
 CODE_TRAIN = 7          # HJBX_CODE_TRAIN(activation) = 7 + activation: the parameter-gradient unit of a user-defined system
+CODE_HESSIAN = 10       # HJBX_CODE_HESSIAN(head, activation) = 10 + 3 * head + activation: the value-Hessian unit of a user-defined system
 _HEADS = {"pd": 0, "soft": 1}
 _ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sin": ACT_SIN}
 
@@ -59,7 +60,8 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds the device headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
 _HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_hessian_kernels.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
-            "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
+            "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_user_hessian_kernels.hpp",
+            "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
 class HjbxAdamState(C.Structure):
@@ -452,10 +454,15 @@ class SystemHandle:
         """hjbx_system_code_object: the gfx950 ELF this user-defined system runs.  which = "streaming" (compiled at creation) or
         (head, activation) with head in ("pd", "soft") and activation in ("relu", "tanh", "sin"): the matrix-core unit, or
         ("train", activation): the parameter-gradient unit (the four k_train_coop kernels of hjbx_value_loss_grad_f32 /
-        hjbx_value_loss_adam_f32) -- compiled now if it has not been.  NotImplementedError when the handle has not enabled the matrix-core kernels or the library refuses to ship the
+        hjbx_value_loss_adam_f32), or ("hessian", head, activation): the value-Hessian unit (the one k_value_hessian kernel of
+        hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32; none for ("hessian", "soft", "relu"): that H is identically zero) --
+        compiled now if it has not been.  NotImplementedError when the handle has not enabled the matrix-core kernels or the library refuses to ship the
         unit, ValueError (with the compiler's log) when the source does not compile there."""
         if which == "streaming":
             code = CODE_STREAMING
+        elif which[0] == "hessian":
+            _, head, act = which
+            code = CODE_HESSIAN + 3 * _HEADS[head] + _ACTIVATIONS[act]
         else:
             head, act = which
             code = CODE_TRAIN + _ACTIVATIONS[act] if head == "train" else 1 + 3 * _HEADS[head] + _ACTIVATIONS[act]

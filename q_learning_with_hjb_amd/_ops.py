@@ -339,7 +339,9 @@ def value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
 
 def value_hessian(sys, mlp_desc, x, want_hessian=True, want_jacobian=False):
     """hjbx_value_hessian_f32: H (B, n, n) = d2V/dx2 and dy_dx (B, n, h3) = d(last layer)/d(error coordinates) of the PD value network on the
-    matrix cores (f32 only; None for an output that is not asked for)."""
+    matrix cores (f32 only; None for an output that is not asked for).  The built-in systems, and a user-defined system whose handle asked
+    for the matrix-core kernels (the first call for an activation compiles its kernel); NotImplementedError for a user-defined system that
+    has not asked, or whose kernel the library refuses because it would need scratch."""
     B = x.shape[0]
     _chk(x, "x", (B, sys.n), torch.float32)
     H = torch.empty((B, sys.n, sys.n), dtype=x.dtype, device=x.device) if want_hessian else None
@@ -360,8 +362,9 @@ def softpd_value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
 
 def softpd_value_hessian(sys, mlp_desc, x):
     """hjbx_softpd_value_hessian_f32: H (B, n, n) = d2V/dx2 of the soft-PD value network (mlp_desc: _abi.HjbxSoftpdMlp) on the matrix cores
-    (f32 only; relu: zeros).  ValueError for a wrong shape or dtype, NotImplementedError for what the library refuses (a user-defined
-    system, a linear system with n outside {2, 4, 6})."""
+    (f32 only; relu: zeros).  A user-defined system whose handle asked for the matrix-core kernels runs its own kernel, compiled at the
+    first call for an activation.  ValueError for a wrong shape or dtype, NotImplementedError for what the library refuses (a user-defined
+    system that has not asked or whose kernel would need scratch, a linear system with n outside {2, 4, 6})."""
     B = x.shape[0]
     if x.dtype != torch.float32:
         raise ValueError(f"x has dtype {x.dtype}, expected {torch.float32}")

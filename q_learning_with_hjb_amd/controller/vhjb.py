@@ -319,8 +319,8 @@ class SoftPDValueFunctionApproximator(torch.nn.Module):
     @torch.no_grad()
     def fused_value_hessian(self, x: torch.Tensor) -> torch.Tensor:
         """d2V/dx2 (B, n, n) from the matrix-core kernel hjbx_softpd_value_hessian_f32 (float32; columns are computed one by one, so H is
-        symmetric up to rounding only; relu: zeros).  NotImplementedError for what the library refuses (a user-defined system, a linear
-        system with n outside {2, 4, 6})."""
+        symmetric up to rounding only; relu: zeros).  NotImplementedError for what the library refuses (a user-defined system without
+        matrix_cores or whose kernel would need scratch, a linear system with n outside {2, 4, 6})."""
         for w in self.layers:
             assert w.is_contiguous() and w.dtype == torch.float32
         return _ops.softpd_value_hessian(self.dynamics.system, self.descriptor(), x)
@@ -575,6 +575,7 @@ class VHJBController(Controller):
         if self.fused_value_grad and not fusable:
             raise NotImplementedError(f"no fused value-gradient kernel for the {activation} activation")
         self.fused_param_grad = self._choose_fused_param_grad(dynamics, config, dtype, activation, soft, self.device, fused_param_grad)
+        self._user_hessian_refused = False     # value_hessian: the library refused this user system's Hessian unit (it would need scratch)
         # fused rollouts of big batches re-pack live environments every `compaction_interval` steps (0 = never)
         self.compaction_interval, self.compaction_min_batch = 16, 8192
         self.train_mode = False
@@ -675,13 +676,18 @@ class VHJBController(Controller):
     def value_hessian(self, x: torch.Tensor) -> torch.Tensor:
         """d2V/dx2 (B, n, n) for a (B, n) device batch, for either value network: the matrix-core kernel where this controller runs the fused
         value network, the torch closed form of the module's value_hessian otherwise -- and for a soft-PD network on a system the library has
-        no kernel for (a linear system with n outside {2, 4, 6})."""
+        no kernel for (a linear system with n outside {2, 4, 6}).  A user-defined system takes the kernel when its handle asked for the
+        matrix-core kernels (compiled at the first call); if the library refuses that unit (it would need scratch) the controller remembers
+        it and returns the closed form, for either head."""
         vf = self.value_function_approximator
-        if self.fused_value_grad and x.dtype == torch.float32 and self.dynamics.system.kind != _abi.SYS_USER:
+        user = self.dynamics.system.kind == _abi.SYS_USER
+        if self.fused_value_grad and x.dtype == torch.float32 and not (user and (self._user_hessian_refused or not self.dynamics.system.matrix_cores)):
             try:
                 return vf.fused_value_hessian(x)
             except NotImplementedError:
-                if self.value_structure != "soft_pd":      # (only the soft-PD network falls back: a refusal for the PD network is the caller's to see)
+                if user:
+                    self._user_hessian_refused = True
+                elif self.value_structure != "soft_pd":    # (only the soft-PD network falls back: a refusal for the PD network is the caller's to see)
                     raise
         return vf.value_hessian(x)
 

@@ -57,6 +57,7 @@ extern "C" int hjbx_value_hessian_f32(const hjbx_system* sys, const hjbx_mlp* ml
     if (!sys || !mlp) return hjbx_set_error(HJBX_EINVAL, "%s: NULL system or mlp descriptor", who);
     const hjbx_net net = make_net(mlp);
     if (const int rc = check_value_hessian(who, sys, net, x, H, dy_dx, B)) return rc == kEmptyCall ? HJBX_OK : rc;
+    if (hjbx_user_matrix_cores(sys)) return hjbx_user_value_hessian(sys, net, x, H, dy_dx, B, stream, who);   // (compiled at its first use)
 #define HJBX_HESS_ENTRY(prefix, v) prefix##_value_hessian_act##v,
     static mlp_value_hessian_fn* const variants[] = {HJBX_HESS_VARIANTS(HJBX_HESS_ENTRY)};
 #undef HJBX_HESS_ENTRY

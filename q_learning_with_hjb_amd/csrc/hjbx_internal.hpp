@@ -45,6 +45,12 @@ struct hjbx_rollout_args {
 bool hjbx_user_matrix_cores(const hjbx_system* s);
 int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float* x, float* V, float* g, int64_t B, void* stream, const char* who);
 int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_net& net, const hjbx_rollout_args& a, const char* who);
+// The Hessian of the value network for such a handle: called by hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32 AFTER
+// check_value_hessian (and after the soft-PD entry point's ReLU memset: no soft-PD ReLU unit exists).  The first call for a (head, activation)
+// compiles the handle's Hessian unit (hjbx_user_hessian_kernels.hpp: k_value_hessian<UserSystem<float>, kHessWaves, activation, head>);
+// HJBX_EUNSUPPORTED when the kernel needs scratch (the refusal is remembered, nothing is launched), HJBX_EINVAL when the source does not
+// compile there.  dy = NULL for the soft-PD head.
+int hjbx_user_value_hessian(const hjbx_system* s, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B, void* stream, const char* who);
 
 // The parameter gradient of such a handle (hjbx_train_coop.hip calls both after the entry points' argument checks).  hjbx_user_train_unit:
 // the handle's train unit for `activation` (hjbx_user_train_kernels.hpp: k_train_coop<0|1, activation, 1|4, UserSystem<float>>), compiled now

@@ -76,14 +76,16 @@ inline int check_value_grad(const char* who, const hjbx_system* sys, const hjbx_
 }
 
 // hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32 after their NULL-descriptor check: the checks of check_value_grad in its order, for
-// these entry points' outputs (dy = dy_dx, PD head only: the soft-PD entry point passes NULL); no kernel exists for a user-defined system
+// these entry points' outputs (dy = dy_dx, PD head only: the soft-PD entry point passes NULL); a user-defined system has a kernel only when
+// its handle asked for the matrix-core kernels (hjbx_user_value_hessian of hjbx_user.hip compiles it at the first call)
 inline int check_value_hessian(const char* who, const hjbx_system* sys, const hjbx_net& net, const float* x, const float* H, const float* dy, int64_t B) {
     if (B < 0) return hjbx_set_error(HJBX_EINVAL, "%s: negative batch size", who);
     if (B == 0 || (!H && !dy)) return kEmptyCall;
     if (!x || !net.W1 || !net.W2 || !net.W3 || (net.soft && (!net.b1 || !net.b2 || !net.b3 || !net.w4 || !net.b4)))
         return hjbx_set_error(HJBX_EINVAL, net.soft ? "%s: NULL x, weight or bias pointer" : "%s: NULL x or weight pointer", who);
-    if (sys->kind == HJBX_SYS_USER)
-        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: user-defined systems are not supported, the kernel exists for the built-in systems only", who);
+    if (sys->kind == HJBX_SYS_USER && !hjbx_user_matrix_cores(sys))
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: user-defined systems are not supported unless the handle has asked for the matrix-core kernels "
+                                                 "(hjbx_system_enable_matrix_cores)", who);
     if (int rc = check_features(who, net)) return rc;
     if (!state_rows_aligned(x, sys) || (reinterpret_cast<uintptr_t>(H) & 15u) || (reinterpret_cast<uintptr_t>(dy) & 15u))
         return hjbx_set_error(HJBX_EINVAL, net.soft ? "%s: x must be aligned to its row vector width, H to 16 bytes"

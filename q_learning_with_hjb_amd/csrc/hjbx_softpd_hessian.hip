@@ -52,6 +52,7 @@ extern "C" int hjbx_softpd_value_hessian_f32(const hjbx_system* sys, const hjbx_
         if (e != hipSuccess) return hjbx_set_error(HJBX_EHIP, "%s: %s", who, hipGetErrorString(e));
         return HJBX_OK;
     }
+    if (hjbx_user_matrix_cores(sys)) return hjbx_user_value_hessian(sys, net, x, H, nullptr, B, stream, who);   // (compiled at its first use)
 #define HJBX_SOFTPD_HESS_ENTRY(prefix, v) prefix##_value_hessian_act##v,
     static mlp_value_hessian_fn* const variants[] = {nullptr, HJBX_SOFTPD_HESS_VARIANTS(HJBX_SOFTPD_HESS_ENTRY)};   // (variant = hjbx_activation)
 #undef HJBX_SOFTPD_HESS_ENTRY

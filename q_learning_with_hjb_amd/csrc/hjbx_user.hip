@@ -9,7 +9,10 @@
 // hjbx_softpd.hip hand an enabled user handle over to hjbx_user_value_grad / hjbx_user_rollout below.  The parameter gradient
 // (hjbx_value_loss_grad_f32 / hjbx_value_loss_adam_f32) is a third unit, hjbx_user_train_kernels.hpp: the cooperative kernel k_train_coop
 // for the user's struct, one unit per activation (PD head only), compiled at its first use and refused as a whole when one of its four
-// kernels needs scratch; hjbx_train_coop.hip builds the arguments and launches it through hjbx_user_train_launch below.
+// kernels needs scratch; hjbx_train_coop.hip builds the arguments and launches it through hjbx_user_train_launch below.  The Hessian of the
+// value network (hjbx_value_hessian_f32 / hjbx_softpd_value_hessian_f32) is a fourth unit, hjbx_user_hessian_kernels.hpp: k_value_hessian
+// for the user's struct, one kernel per (head, activation), compiled at its first use; hjbx_hessian.hip and hjbx_softpd_hessian.hip hand an
+// enabled user handle over to hjbx_user_value_hessian below.
 //
 // hiprtc is opened with dlopen at first use: libhjbx.so has no link-time dependency on it, and a process that never creates a user system
 // never loads it.  Compilation needs no GPU (the CPU test compiles a snippet); modules are loaded per device at the first launch.
@@ -46,6 +49,8 @@
     X(hjbx_src_mlp_h2, "hjbx_mlp_h2.hpp", "hjbx_mlp_h2.hpp")                        \
     X(hjbx_src_train_coop, "hjbx_train_coop_kernels.hpp", "hjbx_train_coop_kernels.hpp") \
     X(hjbx_src_user_train, "hjbx_user_train_kernels.hpp", "hjbx_user_train_kernels.hpp") \
+    X(hjbx_src_hessian_kernels, "hjbx_hessian_kernels.hpp", "hjbx_hessian_kernels.hpp") \
+    X(hjbx_src_user_hessian, "hjbx_user_hessian_kernels.hpp", "hjbx_user_hessian_kernels.hpp") \
     X(hjbx_src_abi, "../../include/hjbx.h", "hjbx.h")
 #if !defined(__HIP_DEVICE_COMPILE__)
 #ifndef HJBX_CSRC_DIR
@@ -142,6 +147,8 @@ struct UserProgram {
     UserUnit mc[2][3];                               // [head: 0 PD, 1 soft-PD][hjbx_activation]
     std::mutex train_mu;                             // guards the state of train[] (held across a lazy compile)
     UserUnit train[3];                               // [hjbx_activation]: the parameter-gradient unit (hjbx_user_train_kernels.hpp), PD head
+    std::mutex hess_mu;                              // guards the state of hess[][] (held across a lazy compile)
+    UserUnit hess[2][3];                             // [head][hjbx_activation]: the value-Hessian unit (hjbx_user_hessian_kernels.hpp); [1][relu] stays empty
 };
 
 // Compile `top` (one #include line) for the user's snippet with the library's own flags + `extra`; name expressions are resolved into
@@ -341,6 +348,26 @@ int train_unit(const hjbx_system* s, int act, const char* who, UserUnit** out) {
                               "the 512 registers of the cooperative parameter-gradient kernel; the fused parameter gradient is refused for this system"}; },
                      who, out);
 }
+
+// The value-Hessian unit of an enabled handle for (head, activation), compiled now if this is the first call that needs it: one kernel, one
+// wave per SIMD and 512 registers; when it needs scratch the unit is refused, the code object dropped and the refusal remembered -- the handle
+// keeps its streaming, matrix-core and train units.  No soft-PD ReLU unit exists: that Hessian is identically zero.
+int hessian_unit(const hjbx_system* s, int soft, int act, const char* who, UserUnit** out) {
+    UserProgram* u = s->kind == HJBX_SYS_USER ? static_cast<UserProgram*>(s->user) : nullptr;
+    if (!u) return hjbx_set_error(HJBX_EINVAL, "%s: not a user-defined system", who);
+    if (soft < 0 || soft > 1 || act < 0 || act > 2) return hjbx_set_error(HJBX_EINVAL, "%s: unknown head %d / activation %d", who, soft, act);
+    if (!hjbx_user_matrix_cores(s))
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: this user-defined system has not asked for the matrix-core kernels (hjbx_system_enable_matrix_cores)", who);
+    if (soft && act == HJBX_ACT_RELU)
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: the Hessian of a soft-PD ReLU network is identically zero (H is filled with zeros): there is no kernel and no code object", who);
+    std::lock_guard<std::mutex> lock(u->hess_mu);
+    return lazy_unit(u, u->hess[soft][act], [&] { return
+                     UnitSpec{"#include \"hjbx_user_hessian_kernels.hpp\"\n", "hjbx_user_hessian.hip",
+                              {"-DHJBX_USER_MLP_ACT=" + std::to_string(act), "-DHJBX_USER_MLP_SOFT=" + std::to_string(soft)},
+                              {"HJBX_UH_VALUE_HESSIAN"}, {"value-Hessian"},
+                              "activation " + std::to_string(act) + (soft ? ", soft-PD head" : ", PD head"), "the 512 registers of the Hessian kernel"}; },
+                     who, out);
+}
 }  // namespace
 
 extern "C" size_t hjbx_last_compile_log(char* buf, size_t buflen) {
@@ -360,6 +387,8 @@ void hjbx_user_release(void* up) {
     for (auto& head : u->mc)
         for (UserUnit& unit : head) unload_unit(unit);
     for (UserUnit& unit : u->train) unload_unit(unit);
+    for (auto& head : u->hess)
+        for (UserUnit& unit : head) unload_unit(unit);
     delete u;
 }
 
@@ -423,9 +452,11 @@ extern "C" size_t hjbx_system_code_object(const hjbx_system* sys, int which, voi
     if (!u) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: not a user-defined system"); return 0; }
     const UserUnit* unit = &u->stream;
     if (which != HJBX_CODE_STREAMING) {
-        if (which < 1 || which > 9) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: unknown code object %d", which); return 0; }
+        if (which < 1 || which > 15) { hjbx_set_error(HJBX_EINVAL, "hjbx_system_code_object: unknown code object %d", which); return 0; }
         UserUnit* mc = nullptr;
-        if (which >= 7) {
+        if (which >= 10) {
+            if (hessian_unit(sys, (which - 10) / 3, (which - 10) % 3, "hjbx_system_code_object", &mc) != HJBX_OK) return 0;
+        } else if (which >= 7) {
             if (train_unit(sys, which - 7, "hjbx_system_code_object", &mc) != HJBX_OK) return 0;
         } else if (matrix_core_unit(sys, (which - 1) / 3, (which - 1) % 3, "hjbx_system_code_object", &mc) != HJBX_OK) {
             return 0;
@@ -487,6 +518,25 @@ int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_ne
                      (void*)&r.env_order, &o, (void*)&r.B, &ngroups, &ws, &sched, net.soft ? (void*)&soft : (void*)&pd};
         return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[r.integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
                            r.stream, who);
+    });
+}
+
+// ---- the value-network Hessian of an enabled handle (called by hjbx_hessian.hip / hjbx_softpd_hessian.hip after check_value_hessian) ---------
+// launch_value_hessian of hjbx_mlp_host.hpp for the handle's own unit: 32 / n samples per tile group, kHessWaves waves per workgroup
+int hjbx_user_value_hessian(const hjbx_system* s, const hjbx_net& net, const float* x, float* H, float* dy, int64_t B, void* stream, const char* who) {
+    UserUnit* unit = nullptr;
+    if (int rc = hessian_unit(s, net.soft, net.activation, who, &unit)) return rc;
+    return with_mc_dims(s, who, "Hessian kernel", [&](auto Nc, auto) -> int {
+        constexpr int N = decltype(Nc)::value;
+        auto blob = user_blob<float>(s);
+        MlpP<N> p = make_mlp_params<N>(net);
+        int64_t ngroups = 0, grid = 0;
+        if (int rc = mlp_persistent_grid(B, 32 / N, &ngroups, &grid, who)) return rc;
+        MlpHeadSoft soft = make_head<MlpHeadSoft>(net);
+        MlpHeadPd pd{};
+        void* a[] = {&blob, &p, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&x, (void*)&H, (void*)&dy, (void*)&B, &ngroups,
+                     net.soft ? (void*)&soft : (void*)&pd};
+        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[0].c_str(), (unsigned)grid, kHessWaves * 64, a, stream, who);
     });
 }
 
