@@ -23,7 +23,9 @@
 //    work (activation, its derivative, |y|^2, 2y) runs in place on the accumulators in VALU-only passes between the
 //    chains, where it overlaps the SIMD partner's MFMAs; activation derivatives are taken from the activations (nothing
 //    extra is stored; layer 1 is recomputed for the last one); the last backward product (only n useful rows) runs on the
-//    VALU.  The activation is a template parameter: ReLU (one integer max) or tanh (exp2 + rcp).
+//    VALU, its W1' rows fetched in groups by the same kind of asm read and counted wait (left to the compiler it was one
+//    exposed LDS latency per feature pair; the chains' own prologues, by contrast, cost nothing measurable: DESIGN 4.2).
+//    The activation is a template parameter: ReLU (one integer max) or tanh (exp2 + rcp).
 //  * Persistent grid, one workgroup per CU (2 waves per SIMD); waves pull tile groups from an LDS counter so SIMD
 //    partners finish together.  In the rollout kernel the per-environment constants (system, task, limits) are staged
 //    in LDS too: as kernel-argument SGPRs they spilled into v_readlane / v_writelane inside the chains.

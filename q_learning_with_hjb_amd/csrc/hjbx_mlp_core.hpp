@@ -119,6 +119,10 @@ template <int ACT> __device__ __forceinline__ float dact1(float h, float d) {
 // retired with counted s_waitcnt lgkmcnt(N) statements fenced by sched_barrier (guide 5.7, form iii; the ISA is
 // audited by tools/audit_asm_loads.py): LDS returns in order, so "at most N newer operations outstanding" means this step's operands have
 // landed.  Any LDS / SMEM operation the compiler adds in between only makes the count conservative.
+// A chain waits for its first DEPTH steps' operands before its first MFMA (seven prologues per tile and step in mlp_value_grad).  Issuing
+// those reads in front of the VALU pass that precedes the chain, and running backward 2 and the layer-1 recomputation through one operand
+// pipeline, were both built and measured (cartpole, B = 2^20): no difference beyond run-to-run spread, alone or together, so the chain
+// keeps its prologue (profiles/rollout_boundaries.json).
 template <int BYTE_OFF> __device__ __forceinline__ float lds_read_b32(uint32_t addr) {
     static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536, "ds_read_b32 offset field is 16 bits");
     float v;
@@ -341,6 +345,89 @@ template <int FB, int R> __device__ __forceinline__ void mask_apply_block(f32x16
     }
 }
 
+// ---- backward 1 (the VALU product at the end of mlp_value_grad) in groups of features ------------------------------------------------------
+// Left to hipcc, every W1' row is read -> s_waitcnt lgkmcnt(0 / 1) -> used by its two v_pk_fma_f32: one LDS latency per feature pair in the open,
+// 32 per tile and step, with nothing of this wave's to put under it.  Here the rows of a whole group of G features are fetched by asm
+// ds_read_b128 (one per float4 of a row) while the previous group's FMAs run, and retired by one counted wait per group (lds_wait, as in the
+// chains; audited by tools/audit_asm_loads.py like them).  Two buffers of G rows: 16 registers each for n <= 8, 24 for n = 10 -- the cartpole
+// rollout kernel stays at its 242 VGPRs, and nothing spills anywhere (tests/test_rollout_boundaries_host.py).  Feature f is register f & 15 of
+// accumulator block f >> 4 and the groups walk f = 0..63 as the plain loop did: every sum is the same fmaf chain, bit for bit.
+// Cartpole B = 2^20: 0.7387 -> 0.7327 ms per step; groups of 8 (255 VGPRs) or 2 measure the same (profiles/rollout_boundaries.json).
+// The units compiled at run time for user-defined systems (hjbx_user_mlp_kernels.hpp) keep the plain loop: the run-time compiler's
+// build of the same templates put 0.9 KB per lane into scratch with the groups (n = 4; hipcc -S of the same unit: none), and a kernel with
+// scratch is refused there.
+#ifdef HJBX_USER_MATRIX_CORE_UNIT
+static constexpr bool kW1tGroups = false;
+#else
+static constexpr bool kW1tGroups = true;
+#endif
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+template <int BYTE_OFF> __device__ __forceinline__ f32x4 lds_read_b128(uint32_t addr) {
+    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 16 == 0, "");
+    f32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(BYTE_OFF));
+    return v;
+}
+template <int NP> struct W1tGroup {
+    static constexpr int Q = NP / 4;             // float4s per row of W1'
+    static constexpr int G = NP <= 4 ? 4 : 2;    // features per group
+    static constexpr int READS = G * Q;          // ds_read_b128 per group = entries of the counted wait
+    static_assert(64 % G == 0 && READS <= 15, "lgkmcnt is a 4-bit field");
+};
+// rows of the features F0 .. F0 + G - 1 into buf; base = LDS byte address of W1'[4h][0] (MlpCtx::w1t)
+template <int NP, int F0, int J = 0> __device__ __forceinline__ void w1t_issue(f32x4 (&buf)[W1tGroup<NP>::READS], uint32_t base) {
+    constexpr int Q = W1tGroup<NP>::Q;
+    if constexpr (J < W1tGroup<NP>::READS) {
+        constexpr int f = F0 + J / Q, q = J % Q;
+        buf[J] = lds_read_b128<((32 * (f >> 4) + perm(f & 15)) * Q + q) * 16>(base);
+        w1t_issue<NP, F0, J + 1>(buf, base);
+    }
+}
+template <int NP, int J = 0> __device__ __forceinline__ void w1t_landed(const f32x4 (&buf)[W1tGroup<NP>::READS]) {
+    if constexpr (J < W1tGroup<NP>::READS) {
+        asm volatile("" : : "v"(buf[J]));
+        w1t_landed<NP, J + 1>(buf);
+    }
+}
+// group GI and the ones behind it: part[k] += W1'[f][2k, 2k + 1] . d1[f] act'(a1[f]).  Order inside a group: asm reads of group GI + 1 |
+// this group's back-propagation factors (they need no weights and run under the reads) | counted wait | this group's FMAs.
+template <int ACT, int NP, int GI = 0>
+__device__ __forceinline__ void w1t_backward(const f32x16 (&a1)[4], const f32x16 (&d1)[4], f32x2 (&part)[NP / 2], f32x4 (&wbuf)[2][W1tGroup<NP>::READS],
+                                             uint32_t base) {
+    constexpr int G = W1tGroup<NP>::G, Q = W1tGroup<NP>::Q, NG = 64 / G;
+    if constexpr (GI < NG) {
+        if constexpr (GI + 1 < NG) w1t_issue<NP, (GI + 1) * G>(wbuf[(GI + 1) & 1], base);
+        __builtin_amdgcn_sched_barrier(0);
+        float dv[G];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int kb = (GI * G + j) >> 4, s = (GI * G + j) & 15;
+            dv[j] = dact1<ACT>(ACT == HJBX_ACT_RELU ? a1[kb][s] : ACT == HJBX_ACT_SIN ? cos1(a1[kb][s]) : act1<ACT>(a1[kb][s]), d1[kb][s]);
+            if constexpr (ACT == HJBX_ACT_SIN) {   // (fenced one by one: see layer 2 of mlp_value_grad)
+                asm volatile("" : "+v"(dv[j]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        lds_wait<(GI + 1 < NG) ? W1tGroup<NP>::READS : 0>();
+        // A row is padded to whole float4s (n = 2, 6, 10: two columns of the last one feed nothing).  The compiler tracks liveness per
+        // register, so it handed the unused half of such a destination to other values while the read, which writes all four, was in
+        // flight.  One use of the WHOLE vector behind the wait keeps all of it allocated until it has landed (no instruction).
+        w1t_landed<NP>(wbuf[GI & 1]);
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const f32x2 dv2{dv[j], dv[j]};
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {   // packed pairs: one v_pk_fma_f32 per two rows of W1
+                const f32x4 w = wbuf[GI & 1][j * Q + q];
+                part[2 * q + 0] = __builtin_elementwise_fma(f32x2{w[0], w[1]}, dv2, part[2 * q + 0]);
+                part[2 * q + 1] = __builtin_elementwise_fma(f32x2{w[2], w[3]}, dv2, part[2 * q + 1]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        w1t_backward<ACT, NP, GI + 1>(a1, d1, part, wbuf, base);
+    }
+}
+
 // V and dV/dx of the TL tiles whose state rows are in xs (one environment per lane, identical in both lane
 // halves).  On return every lane holds its environment's V and (if want_grad) gradient.
 // SOFT selects the head: false (PD, controller/vhjb.py) V = |y|^2 + eps_s |e|^2, dV/dy = 2y;  true (soft-PD, `bias` = the LDS copy of
@@ -496,31 +583,41 @@ __device__ __forceinline__ void mlp_value_grad(const S& sys, const MlpP<S::N>& p
     // lane dots its 64 resident features with W1' rows (wave-uniform float4 LDS broadcasts) and the two lane
     // halves are added with one cross-half shuffle per row.  [h1 > 0] is re-derived by recomputing layer 1
     // (N/2 x 4 MFMAs, 1 % of the tile): cheaper in issue slots than carrying 128 mask bits per lane.
+    // The W1' rows come in groups through w1t_backward; the first group's reads go out in front of the recomputation chain (older than the
+    // chain's own reads, so its counted waits retire them first) and land under its MFMAs.
     if constexpr (SOFT) bias_acc(a1, bias->b1, h);
     else zero_acc(a1);
+    const uint32_t w1t = (uint32_t)(uintptr_t)c.w1t;   // (LDS byte address, as in mlp_ctx)
+    f32x4 wbuf[2][W1tGroup<NP>::READS];
+    if constexpr (kW1tGroups) w1t_issue<NP, 0>(wbuf[0], w1t);
     mfma_chain<OffW1F, N / 2, 4, 2, TL>(a1, ring4, c.w1f, [&](int st, int t) { return h ? z[t][2 * st + 1] : z[t][2 * st]; });
 #pragma unroll
     for (int t = 0; t < TL; ++t) {
-        f32x2 part[NP / 2];  // packed pairs: one v_pk_fma_f32 per two rows of W1
+        f32x2 part[NP / 2];
 #pragma unroll
         for (int k = 0; k < NP / 2; ++k) part[k] = f32x2{0.f, 0.f};
+        if constexpr (kW1tGroups) {
+            if (t > 0) w1t_issue<NP, 0>(wbuf[0], w1t);
+            w1t_backward<ACT, NP>(a1[t], d1[t], part, wbuf, w1t);
+        } else {
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
+            for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                float dv = dact1<ACT>(ACT == HJBX_ACT_RELU ? a1[t][kb][s] : ACT == HJBX_ACT_SIN ? cos1(a1[t][kb][s]) : act1<ACT>(a1[t][kb][s]), d1[t][kb][s]);
-                if constexpr (ACT == HJBX_ACT_SIN) {
-                    asm volatile("" : "+v"(dv));
-                    __builtin_amdgcn_sched_barrier(0);
+                for (int s = 0; s < 16; ++s) {
+                    float dv = dact1<ACT>(ACT == HJBX_ACT_RELU ? a1[t][kb][s] : ACT == HJBX_ACT_SIN ? cos1(a1[t][kb][s]) : act1<ACT>(a1[t][kb][s]), d1[t][kb][s]);
+                    if constexpr (ACT == HJBX_ACT_SIN) {
+                        asm volatile("" : "+v"(dv));
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    const f32x2 dv2{dv, dv};
+#pragma unroll
+                    for (int q = 0; q < NP / 4; ++q) {
+                        const float4 w = c.w1t[(32 * kb + perm(s)) * (NP / 4) + q];
+                        part[2 * q + 0] = __builtin_elementwise_fma(f32x2{w.x, w.y}, dv2, part[2 * q + 0]);
+                        part[2 * q + 1] = __builtin_elementwise_fma(f32x2{w.z, w.w}, dv2, part[2 * q + 1]);
+                    }
                 }
-                const f32x2 dv2{dv, dv};
-#pragma unroll
-                for (int q = 0; q < NP / 4; ++q) {
-                    const float4 w = c.w1t[(32 * kb + perm(s)) * (NP / 4) + q];
-                    part[2 * q + 0] = __builtin_elementwise_fma(f32x2{w.x, w.y}, dv2, part[2 * q + 0]);
-                    part[2 * q + 1] = __builtin_elementwise_fma(f32x2{w.z, w.w}, dv2, part[2 * q + 1]);
-                }
-            }
+        }
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             const float pk = part[k >> 1][k & 1];
