@@ -590,6 +590,50 @@ int hjbx_rollout_cost_stats_f64(const double* cost, const int32_t* done_step, in
 #define HJBX_HAS_ACTIVATION_PROBE 1 /* the entry point below exists (an addition, nothing else changed) */
 int hjbx_activation_probe_f32(int activation, const float* a, float* h, float* s, int64_t N, void* stream);
 
+/* The min-snap waypoint planner of Quadrotors2D on the device (quadrotors_model_based_controller.py:77-233).  The host solves the 7th-order
+ * polynomials through the waypoints (solve_minimum_snap_coefficient, :99-159, float64); these entry points evaluate `update(t)` (:218-233):
+ * the segment = the last i with t >= cumulated_t[i], the local time t - cumulated_t[i], derivatives 0..4 of both polynomials (:161-176) and the
+ * differential flatness map to [x, y, theta, xd, yd, thetad] and the two rotor thrusts (:178-216), in the reference's formulas -- its theta_ddot
+ * expression included, which is not the exact second derivative of theta (u_ref is not an exact feedforward).  Past the
+ * last waypoint the reference is a hover at end_pt with local time 0 (:220-225).
+ *   sys: a HJBX_SYS_QUAD2D handle (m, r, I, g, dt and the control limits are read from it).
+ *   coeff (n_plans, 2, S, 8): ascending powers, the reference's layout (axis, segment, power); cum_t (n_plans, S + 1) = cumulated_t, ALWAYS
+ *   double: segment and local time are found in float64 in both precisions, only the local time is rounded; end_pt (n_plans, 2) = points[-1].
+ *   n_plans = 1: one plan shared by the B environments; n_plans = B: plan b belongs to environment b.
+ *   t_k = t0 + k dt, formed in double for every k (never accumulated).
+ * hjbx_minsnap_reference_*: x_ref (T_steps, B, 6), u_ref (T_steps, B, 2) = update(t_k) for k < T_steps, time-major; either may be NULL.
+ * The segment index is held to [0, S] whatever cum_t contains: no plan leads a load outside coeff.
+ * HJBX_EINVAL before any launch: a NULL handle or one that is not HJBX_SYS_QUAD2D, S < 1, t0 < 0 (or NaN), T_steps < 0, B < 0, n_plans other
+ * than 1 or B, NULL or misaligned coeff (16 bytes), cum_t (8 bytes) or end_pt (its row), a misaligned output.  B == 0 or T_steps == 0:
+ * HJBX_OK, nothing launched. */
+#define HJBX_HAS_MINSNAP 1 /* the four entry points below exist (an addition, nothing else changed) */
+/* (quadrotors_model_based_controller.py:218-233 and :178-216 in float32) */
+int hjbx_minsnap_reference_f32(const hjbx_system* sys, const float* coeff, const double* cum_t, const float* end_pt, int S, int64_t n_plans,
+                               double t0, int T_steps, float* x_ref, float* u_ref, int64_t B, void* stream);
+/* (quadrotors_model_based_controller.py:218-233 and :178-216 in float64) */
+int hjbx_minsnap_reference_f64(const hjbx_system* sys, const double* coeff, const double* cum_t, const double* end_pt, int S, int64_t n_plans,
+                               double t0, int T_steps, double* x_ref, double* u_ref, int64_t B, void* stream);
+
+/* The tracking closed loop on a plan, one kernel launch: for k < T_steps
+ *   (x_ref, u_ref) = update(t_k);  e = states_wrap(x_k - x_ref);  u_k = clip(u_ref - K e, umin, umax)      (the law of :36-38 about a moving reference)
+ *   cost_k = (e'Qe + (u_k - u_ref)'R(u_k - u_ref)) dt;  x_{k+1} = Dynamics.simulate(x_k, u_k)              (dynamics_basic.py:107-122; HJBX_RK4: u held)
+ *   ctrl: HJBX_CTRL_LINEAR_FEEDBACK, only K (2, 6) is read; task: Q and R of the step cost, NULL when neither cost output is asked for.
+ *   x0 (B, 6).  Outputs, time-major, each may be NULL: traj (T_steps + 1, B, 6), u_log (T_steps, B, 2), cost (T_steps, B),
+ *   total_cost (B,) = the sum of cost_k in time order, x_final (B, 6), x_ref_log (T_steps, B, 6), u_ref_log (T_steps, B, 2): the two
+ *   reference logs are bit-equal to hjbx_minsnap_reference_* on the same plan (one device function).
+ * HJBX_EINVAL before any launch: everything hjbx_minsnap_reference_* refuses, a NULL controller or one of another kind, an integrator other
+ * than HJBX_EULER / HJBX_RK4, a cost output without a task, NULL or misaligned x0, a misaligned output.  B == 0: HJBX_OK, nothing launched. */
+/* (quadrotors_model_based_controller.py:36-38 about update(t) of :218-233, float32) */
+int hjbx_rollout_minsnap_tracking_f32(const hjbx_system* sys, const hjbx_task* task, const hjbx_controller* ctrl, int integrator,
+                                      const float* coeff, const double* cum_t, const float* end_pt, int S, int64_t n_plans, double t0, int T_steps,
+                                      const float* x0, float* traj, float* u_log, float* cost, float* total_cost, float* x_final,
+                                      float* x_ref_log, float* u_ref_log, int64_t B, void* stream);
+/* (quadrotors_model_based_controller.py:36-38 about update(t) of :218-233, float64) */
+int hjbx_rollout_minsnap_tracking_f64(const hjbx_system* sys, const hjbx_task* task, const hjbx_controller* ctrl, int integrator,
+                                      const double* coeff, const double* cum_t, const double* end_pt, int S, int64_t n_plans, double t0,
+                                      int T_steps, const double* x0, double* traj, double* u_log, double* cost, double* total_cost,
+                                      double* x_final, double* x_ref_log, double* u_ref_log, int64_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,7 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_fit.hip", (), "hjbx_fit.o"),
           ("hjbx_replay.hip", (), "hjbx_replay.o"),
           ("hjbx_collect.hip", (), "hjbx_collect.o"),
+          ("hjbx_track.hip", (), "hjbx_track.o"),                                 # min-snap waypoint planner + tracking rollout of Quadrotors2D
           ("hjbx_probe.hip", (), "hjbx_probe.o"),                                 # test infrastructure: act1 / dact1 / sincos1 on a plain array
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=0",), "hjbx_softpd_relu.o"),    # soft-PD network: once per activation, like hjbx_mlp.hip
           ("hjbx_softpd.hip", ("-DHJBX_SOFTPD_ACT=1",), "hjbx_softpd_tanh.o"),
@@ -60,6 +61,7 @@ _UNITS = (("hjbx_kernels.hip", (), "hjbx_kernels.o"),
           ("hjbx_user.hip", (f'-DHJBX_CSRC_DIR="{_CSRC}"',), "hjbx_user.o"))       # embeds the device headers as text for hiprtc (.incbin)
 _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
 _HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_hessian_kernels.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
+            "hjbx_minsnap.hpp",
             "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_user_hessian_kernels.hpp",
             "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
@@ -261,7 +263,8 @@ EXPORTED_SYMBOLS = (
      "hjbx_value_loss_adam_workspace_bytes", "hjbx_value_loss_adam_f32", "hjbx_softpd_value_grad_f32", "hjbx_softpd_rollout_f32",
      "hjbx_replay_append_workspace_bytes", "hjbx_replay_append_f32", "hjbx_replay_append_f64",
      "hjbx_initial_state_philox_f32", "hjbx_initial_state_philox_f64", "hjbx_rollout_cost_stats_f32", "hjbx_rollout_cost_stats_f64",
-     "hjbx_activation_probe_f32", "hjbx_value_hessian_f32", "hjbx_softpd_value_hessian_f32"]
+     "hjbx_activation_probe_f32", "hjbx_value_hessian_f32", "hjbx_softpd_value_hessian_f32",
+     "hjbx_minsnap_reference_f32", "hjbx_minsnap_reference_f64", "hjbx_rollout_minsnap_tracking_f32", "hjbx_rollout_minsnap_tracking_f64"]
     + [f"hjbx_{k}_{s}" for k in _typed_signatures() for s in ("f32", "f64")]
 )
 
@@ -347,6 +350,13 @@ def lib() -> C.CDLL:
             fn = getattr(L, f"hjbx_rollout_cost_stats_{sfx}")
             fn.restype = C.c_int
             fn.argtypes = [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP]
+        for sfx in ("f32", "f64"):
+            fn = getattr(L, f"hjbx_minsnap_reference_{sfx}")       # (sys, coeff, cum_t, end_pt, S, n_plans, t0, T_steps, x_ref, u_ref, B, stream)
+            fn.restype = C.c_int
+            fn.argtypes = [_VP, _VP, _VP, _VP, _I32, _I64, _DBL, _I32, _VP, _VP, _I64, _VP]
+            fn = getattr(L, f"hjbx_rollout_minsnap_tracking_{sfx}")   # (sys, task, ctrl, integrator, the plan as above, x0, 7 outputs, B, stream)
+            fn.restype = C.c_int
+            fn.argtypes = [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _I32, _I64, _DBL, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]
         L.hjbx_activation_probe_f32.restype = C.c_int
         L.hjbx_activation_probe_f32.argtypes = [_I32, _VP, _VP, _VP, _I64, _VP]
         for name, sig in _typed_signatures().items():

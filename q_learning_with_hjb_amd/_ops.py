@@ -327,6 +327,56 @@ def rollout_feedback(sys, ctrl, x0, T_steps, task=None, integrator=_abi.EULER, t
     return dict(traj=traj, u=ulog, cost=cost, done_step=done_step, total_cost=total, x_final=x_final)
 
 
+def _chk_plan(coeff, cum_t, end_pt, B):
+    """-> (S, n_plans) of a device plan: coeff (n_plans, 2, S, 8), cum_t (n_plans, S + 1) float64, end_pt (n_plans, 2); n_plans in {1, B}"""
+    _sfx(coeff)
+    if coeff.dim() != 4 or coeff.shape[1] != 2 or coeff.shape[3] != 8 or coeff.shape[2] < 1:
+        raise ValueError(f"coeff must be (n_plans, 2, S >= 1, 8), got shape {tuple(coeff.shape)}")
+    n_plans, S = coeff.shape[0], coeff.shape[2]
+    if n_plans != 1 and n_plans != B:
+        raise ValueError(f"{n_plans} plans for {B} environments: a plan is shared (1) or there is one per environment")
+    _chk(coeff, "coeff", (n_plans, 2, S, 8))
+    _chk(cum_t, "cum_t", (n_plans, S + 1), torch.float64)
+    _chk(end_pt, "end_pt", (n_plans, 2), coeff.dtype)
+    return S, n_plans
+
+
+def minsnap_reference(sys, coeff, cum_t, end_pt, T_steps, t0=0.0, B=None):
+    """hjbx_minsnap_reference_*: the planner's update(t0 + k dt) for k < T_steps on the plan(s) `coeff` / `cum_t` / `end_pt` (see _chk_plan;
+    B defaults to the number of plans) -> time-major x_ref (T_steps, B, 6), u_ref (T_steps, B, 2) of coeff's dtype."""
+    B = coeff.shape[0] if B is None else int(B)
+    S, n_plans = _chk_plan(coeff, cum_t, end_pt, B)
+    T_steps = int(T_steps)
+    x_ref = torch.empty((max(T_steps, 0), B, 6), dtype=coeff.dtype, device=coeff.device)
+    u_ref = torch.empty((max(T_steps, 0), B, 2), dtype=coeff.dtype, device=coeff.device)
+    check(_fn("minsnap_reference", coeff)(sys.ptr, _p(coeff), _p(cum_t), _p(end_pt), S, n_plans, float(t0), T_steps, _p(x_ref), _p(u_ref), B, _stream()))
+    return x_ref, u_ref
+
+
+def rollout_minsnap_tracking(sys, ctrl, coeff, cum_t, end_pt, x0, T_steps, t0=0.0, task=None, integrator=_abi.EULER, log_traj=True, log_u=True,
+                             log_cost=False, log_reference=False):
+    """hjbx_rollout_minsnap_tracking_*: the closed loop u = clip(u_ref(t) - K wrap(x - x_ref(t))) along a min-snap plan in one kernel launch.
+    Returns a dict of time-major device tensors: traj (T+1, B, 6), u (T, B, 2), cost (T, B), total_cost (B,) (both need `task`), x_final,
+    x_ref (T, B, 6), u_ref (T, B, 2); None for what was not asked for."""
+    B = x0.shape[0]
+    _chk(x0, "x0", (B, 6))
+    S, n_plans = _chk_plan(coeff, cum_t, end_pt, B)
+    if coeff.dtype != x0.dtype or coeff.device != x0.device:
+        raise ValueError(f"the plan is {coeff.dtype} on {coeff.device}, x0 {x0.dtype} on {x0.device}")
+    T_steps = int(T_steps)
+    Tn, dt, dev = max(T_steps, 0), x0.dtype, x0.device
+    traj = torch.empty((Tn + 1, B, 6), dtype=dt, device=dev) if log_traj else None
+    ulog = torch.empty((Tn, B, 2), dtype=dt, device=dev) if log_u else None
+    cost = torch.empty((Tn, B), dtype=dt, device=dev) if (log_cost and task is not None) else None
+    total = torch.empty((B,), dtype=dt, device=dev) if task is not None else None
+    x_final = torch.empty_like(x0)
+    xr = torch.empty((Tn, B, 6), dtype=dt, device=dev) if log_reference else None
+    ur = torch.empty((Tn, B, 2), dtype=dt, device=dev) if log_reference else None
+    check(_fn("rollout_minsnap_tracking", x0)(sys.ptr, ref(task), ref(ctrl), int(integrator), _p(coeff), _p(cum_t), _p(end_pt), S, n_plans, float(t0),
+                                              T_steps, _p(x0), _p(traj), _p(ulog), _p(cost), _p(total), _p(x_final), _p(xr), _p(ur), B, _stream()))
+    return dict(traj=traj, u=ulog, cost=cost, total_cost=total, x_final=x_final, x_ref=xr, u_ref=ur)
+
+
 def value_grad(sys, mlp_desc, x, want_v=True, want_grad=True):
     """Fused MFMA value network forward + input gradient (f32 only)."""
     B = x.shape[0]
