@@ -1,0 +1,234 @@
+"""The one OFF-STOCK configuration of the suite (TEST INFRASTRUCTURE, no GPU needed to import or to build the objects).
+
+The stock values (configs/defaults.py) are degenerate exactly where the kernels have separate code for them: l = m = 1 makes a cached
+reciprocal and a division the same thing, mean = 0 / std = 1 make the normalisation the identity, Q = R = I make Rinv = R = R' and hide every
+off-diagonal, symmetric boxes hide a swapped bound.  Everything here is away from those values, and every number is DYADIC (a short binary
+fraction), so float32 holds it exactly and the float32 kernels, the float-compiled oracle and the float64 oracle start from identical inputs.
+
+tools/gen_golden_offstock.py reads CONSTANTS / LIMITS / DT from this module and writes tests/golden/offstock.npz from the reference's code."""
+import numpy as np
+
+DT = 0.03125
+
+# physical constants (field names of the product's dynamics configs)
+CONSTANTS = {
+    "linear": dict(A=[[-0.25, 1.5], [-0.75, 0.375]], B=[[0.5], [1.25]]),
+    "cartpole": dict(mc=1.75, mp=0.375, l=0.625, g=3.75),
+    "acrobot": dict(m1=1.25, m2=0.75, l1=0.875, l2=1.5, I1=0.3125, I2=0.5625, g=3.75),
+    "quad2d": dict(m=0.625, r=0.3125, I=0.046875, g=3.75),
+    "nearhover": dict(g=3.75, m=1.375, kT=0.8125, n0=7.0),
+}
+# the stock value of each constant (what the sensitivity checks put back)
+STOCK_CONSTANTS = {
+    "linear": dict(A=[[0.0, 1.0], [0.0, 0.0]], B=[[0.0], [1.0]]),
+    "cartpole": dict(mc=1.0, mp=0.1, l=1.0, g=9.81),
+    "acrobot": dict(m1=8.0, m2=8.0, l1=0.5, l2=1.0, I1=2.0, I2=8.0, g=10.0),
+    "quad2d": dict(m=1.0, r=0.25, I=0.0625, g=9.81),
+    "nearhover": dict(g=9.81, m=1.0, kT=0.91, n0=10.0),
+}
+# control box (umin, umax): asymmetric everywhere
+LIMITS = {
+    "linear": ([-3.0], [2.0]),
+    "cartpole": ([-6.0], [9.0]),
+    "acrobot": ([-7.0], [5.0]),
+    "quad2d": ([-4.0, -6.0], [12.0, 10.0]),
+    "nearhover": ([0.5, -6.0, -9.0], [11.0, 8.0, 7.0]),
+}
+DIMS = {"linear": (2, 1), "cartpole": (4, 1), "acrobot": (4, 1), "quad2d": (6, 2), "nearhover": (10, 3)}
+
+# targets: non-zero float32 numbers; the cart-pole and the acrobot stay next to their upright (3.125 = pi - 0.0166)
+XF = {
+    "linear": [0.25, -0.125],
+    "cartpole": [0.25, 3.125, 0.0, 0.0],
+    "acrobot": [3.125, 0.0625, 0.0, 0.0],
+    "quad2d": [0.5, -0.25, 0.0625, 0.0, 0.0, 0.0],
+    "nearhover": [0.25, -0.5, 0.375, 0.03125, -0.0625, 0.0, 0.0, 0.0, 0.0, 0.0],
+}
+UF = {
+    "linear": [0.25],
+    "cartpole": [-0.5],
+    "acrobot": [0.375],
+    "quad2d": [1.25, 1.0],
+    "nearhover": [6.25, 0.5, -0.25],
+}
+# observation box on the error coordinates, obs_min != -obs_max
+OBS = {
+    "linear": ([-1.5, -3.0], [2.0, 2.5]),
+    "cartpole": ([-4.0, -0.375, -6.0, -5.0], [5.0, 0.5, 8.0, 7.0]),
+    "acrobot": ([-0.75, -1.0, -6.0, -8.0], [1.0, 0.875, 8.0, 7.0]),
+    "quad2d": ([-2.0, -1.5, -1.25, -5.0, -4.0, -2.0], [1.75, 2.0, 1.5, 4.0, 5.0, 2.5]),
+    "nearhover": ([-2.0, -1.5, -2.0, -0.5, -0.375, -4.0, -3.0, -4.0, -2.0, -1.5], [1.5, 2.0, 1.75, 0.375, 0.5, 3.0, 4.0, 3.5, 1.5, 2.0]),
+}
+R_DENSE = {
+    1: [[0.625]],
+    2: [[1.5, 0.5], [0.5, 0.75]],
+    3: [[1.5, 0.5, -0.25], [0.5, 1.0, 0.375], [-0.25, 0.375, 0.75]],
+}
+EPSILON = 1e-10
+
+
+def normalization(n):
+    """mean != 0, std != 1, all float32 numbers: the values of test_gpu_value_hessian._controller"""
+    return ([((k % 3) - 1) / 16.0 + 1.0 / 32.0 for k in range(n)], [(0.75, 1.5, 1.25, 2.0, 0.5)[k % 5] for k in range(n)])
+
+
+def dense_Q(n):
+    """SPD by diagonal dominance: diagonal in {1, 1.25, 1.5}, off-diagonals in {-1/16, 0, 1/16} (row sums of |.| <= 9/16)."""
+    i, j = np.indices((n, n))
+    Q = 0.0625 * ((i + j + 1) % 3 - 1.0)
+    Q[np.arange(n), np.arange(n)] = 1.0 + 0.25 * (np.arange(n) % 3)
+    return Q
+
+
+def dense_R(m):
+    return np.array(R_DENSE[m], np.float64)
+
+
+def dense_P(n):
+    """a non-identity SPD terminal cost: 2 Q + 1/8 on the first off-diagonals (still diagonally dominant)"""
+    P = 2.0 * dense_Q(n)
+    k = np.arange(n - 1)
+    P[k, k + 1] += 0.125
+    P[k + 1, k] += 0.125
+    return P
+
+
+def dynamics_kwargs(name, **override):
+    kw = dict(CONSTANTS[name], dt=DT, umin=LIMITS[name][0], umax=LIMITS[name][1])
+    kw.update(override)
+    return kw
+
+
+def make_offstock_dynamics(name, **override):
+    """Product Dynamics object at the off-stock constants (`override`: single fields put back, for sensitivity checks)."""
+    from q_learning_with_hjb_amd.configs import defaults as D
+    from q_learning_with_hjb_amd.dynamics.acrobot import Acrobot
+    from q_learning_with_hjb_amd.dynamics.cartpole import Cartpole
+    from q_learning_with_hjb_amd.dynamics.linear import LinearDynamics
+    from q_learning_with_hjb_amd.dynamics.quadrotors import NearHoverQuadcopter, Quadrotors2D
+    cls, cfg = {"linear": (LinearDynamics, D.linear_dynamics_config), "cartpole": (Cartpole, D.cartpole_dynamics_config),
+                "acrobot": (Acrobot, D.acrobot_dynamics_config), "quad2d": (Quadrotors2D, D.quadrotors2d_dynamics_config),
+                "nearhover": (NearHoverQuadcopter, D.near_hover_dynamics_config)}[name]
+    return cls(cfg(**dynamics_kwargs(name, **override)))
+
+
+def task_kwargs(name):
+    n, m = DIMS[name]
+    mean, std = normalization(n)
+    return dict(xf=list(XF[name]), uf=list(UF[name]), obs_min=list(OBS[name][0]), obs_max=list(OBS[name][1]), Q=dense_Q(n), R=dense_R(m),
+                normalization_mean=mean, normalization_std=std, epsilon=EPSILON)
+
+
+def offstock_vhjb_config(name, **kw):
+    """VHJBControllerConfig with the off-stock task and network normalisation; `kw` overrides (sizes, training options) as in make_vhjb_config."""
+    from conftest import make_vhjb_config
+    d = task_kwargs(name)
+    xf = d["xf"]
+    d.update(interior_states_mean=xf, boundary_states_mean=xf)
+    d.update(kw)
+    if name == "acrobot":    # make_vhjb_config("acrobot") fixes xf and the box itself: the same base (the cart-pole file's hyper-parameters)
+        from q_learning_with_hjb_amd.configs.defaults import cartpole_vhjb_config
+        return cartpole_vhjb_config(**d)
+    return make_vhjb_config(name, **d)
+
+
+def offstock_task(name, **override):
+    """struct hjbx_task of the off-stock task with the dense terminal cost dense_P (a VHJBController solves its own P)."""
+    from q_learning_with_hjb_amd import _abi
+    n, m = DIMS[name]
+    d = dict(task_kwargs(name), P=dense_P(n))
+    d.update(override)
+    return _abi.make_task(n, m, d["Q"], d["R"], d["P"], d["xf"], d["uf"], d["obs_min"], d["obs_max"], d["epsilon"])
+
+
+def task_namespace(name, **override):
+    """what parity_util.step_term_scales reads: R, R_inv, uf, epsilon"""
+    import types
+    d = dict(task_kwargs(name))
+    d.update(override)
+    R = np.asarray(d["R"], np.float64)
+    return types.SimpleNamespace(R=R, R_inv=np.linalg.inv(R), uf=np.asarray(d["uf"], np.float64), epsilon=d["epsilon"], Q=np.asarray(d["Q"], np.float64),
+                                 xf=np.asarray(d["xf"], np.float64))
+
+
+def box_states(name, B, seed, spread=1.0, angle_turns=0.0):
+    """xf + U(obs_min, obs_max) x spread, rates capped at +-3; float64 (B, n).  angle_turns > 0 widens the angle slots to that many pi."""
+    from conftest import ANGLE_IDX
+    rng = np.random.default_rng(seed)
+    lo = np.asarray(OBS[name][0], np.float64).clip(min=-3.0)
+    hi = np.asarray(OBS[name][1], np.float64).clip(max=3.0)
+    if angle_turns:
+        lo[ANGLE_IDX[name]], hi[ANGLE_IDX[name]] = -angle_turns * np.pi, angle_turns * np.pi
+    u = rng.uniform(size=(B, DIMS[name][0]))
+    return np.asarray(XF[name], np.float64) + (lo + u * (hi - lo)) * spread
+
+
+def f32(a):
+    """round to float32, return float64: the inputs every precision starts from"""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def stream_case(name, B=4097, seed=1):
+    """(x, u) of the streaming-kernel tests: states over several periods of the angles, a third of the controls beyond either limit;
+    near-hover roll and pitch within +-1.2 of a multiple of 2 pi (tan's pole is at pi / 2)."""
+    n, m = DIMS[name]
+    rng = np.random.default_rng(seed)
+    x = box_states(name, B, seed + 50, spread=1.5, angle_turns=2.5 if name != "nearhover" else 0.0)
+    if name == "nearhover":
+        x[:, 3:5] = rng.uniform(-1.2, 1.2, (B, 2)) + 2 * np.pi * rng.integers(-2, 3, (B, 2))
+    lo, hi = (np.asarray(v, np.float64) for v in LIMITS[name])
+    u = 0.5 * (hi + lo) + rng.uniform(-1.5, 1.5, (B, m)) * 0.5 * (hi - lo)
+    return f32(x), f32(u)
+
+
+def step_sequence_case(name, B=4097, T=6, seed=33):
+    """start states (a few outside the asymmetric box) and the T + 1 arbitrary value gradients of the vhjb_step sequence"""
+    n, m = DIMS[name]
+    rng = np.random.default_rng(seed)
+    x = box_states(name, B, seed + 1, spread=0.5)
+    x[::3] = box_states(name, B, seed + 2, spread=1.05)[::3]          # a third around the faces of the box: some start outside
+    x = f32(x)
+    # per environment: small gradients (control inside its box, the environment stays live) or large ones (clipped controls)
+    gscale = np.where(rng.uniform(size=(B, 1)) < 0.5, 0.25, 5.0)
+    gs = [f32(rng.standard_normal((B, n)) * gscale) for _ in range(T + 1)]
+    return x, gs
+
+
+def product_controller(name, g):
+    """(dynamics, model-based product controller) at the off-stock constants with the dense Q, R; g: the system's part of the fixture"""
+    d = make_offstock_dynamics(name)
+    n, m = DIMS[name]
+    Q, R = dense_Q(n), dense_R(m)
+    if name == "linear":
+        from q_learning_with_hjb_amd.controller.lqr import LQR
+        return d, LQR(d, Q, R)
+    if name == "cartpole":
+        from q_learning_with_hjb_amd.controller.cartpole_energy_shaping import CartpoleEnergyShapingController
+        return d, CartpoleEnergyShapingController(d, Q=Q, R=R)
+    if name == "acrobot":
+        from q_learning_with_hjb_amd.controller.acrobot_energy_shaping import AcrobotEnergyShapingController
+        return d, AcrobotEnergyShapingController(d, Q=Q, R=R, eps=float(g["eps"]))
+    from q_learning_with_hjb_amd.controller.quadrotors_model_based_controller import NearHoverQuadcopterHoveringController, Quadrotors2DHoveringController
+    cls = Quadrotors2DHoveringController if name == "quad2d" else NearHoverQuadcopterHoveringController
+    return d, cls(d, g["ctrl_xf"], Q, R)
+
+
+def shifted_quadratic_weights(n, P, mean, std, noise=0.02, seed=5, features=(128, 128, 64)):
+    """ReLU weights with V(x) = (e - mean)'P(e - mean) + eps |e|^2 through the NORMALISED input z = (e - mean) / std: load_quadratic's
+    construction (q = L'(e - mean), P = LL', pairs (q, -q) through both hidden layers) with the rows of W1 scaled by std, plus `noise` x a
+    lecun-normal draw on every entry.  float32 numbers, returned as float64 arrays."""
+    h1, h2, h3 = features
+    L = np.linalg.cholesky(np.asarray(P, np.float64))
+    eye = np.eye(n)
+    W1, W2, W3 = np.zeros((n, h1)), np.zeros((h1, h2)), np.zeros((h2, h3))
+    SL = np.asarray(std, np.float64)[:, None] * L
+    W1[:, :n], W1[:, n:2 * n] = SL, -SL
+    W2[:n, :n], W2[n:2 * n, :n], W2[:n, n:2 * n], W2[n:2 * n, n:2 * n] = eye, -eye, -eye, eye
+    W3[:n, :n], W3[n:2 * n, :n] = eye, -eye
+    rng = np.random.default_rng(seed)
+    return [f32(W + noise * rng.standard_normal(W.shape) / np.sqrt(W.shape[0])) for W in (W1, W2, W3)]
+
+
+def rollout_case(name, B=256, seed=4):
+    """start states of the fused rollout's oracle comparison: the box x 1.02, a few outside it (terminal at step 0)"""
+    return f32(box_states(name, B, seed, spread=1.02))

@@ -65,9 +65,15 @@ def assert_within_cpu_yardstick(label, got, cpu32, want, scale, angle_idx=(), ke
     return sg, sc
 
 
+def _offdiag(M):
+    """|M| with its diagonal set to zero"""
+    A = np.abs(np.asarray(M, np.float64))
+    return A - np.diag(np.diag(A))
+
+
 def step_term_scales(name, d, ctl, s, xr, g, gabs, ou, oc, integ="euler"):
-    """`ctl`: anything with R, R_inv, uf, epsilon (a VHJBController, or a namespace).  gabs >= |g|: the term scale of dV/dx (|g| itself when the
-    gradient is an input).  Per element: the sum of the magnitudes of the terms that make up u, x', cost and the residual of ONE closed-loop step (float64),
+    """`ctl`: anything with R, R_inv, uf, epsilon (a VHJBController, or a namespace), and for a dense Q also Q and xf.  gabs >= |g|: the term scale
+    of dV/dx (|g| itself when the gradient is an input).  Per element: the sum of the magnitudes of the terms that make up u, x', cost and the residual of ONE closed-loop step (float64),
     each including what the allowed error of the quantities it is computed from contributes.  bound = RTOL x these."""
     from oracle import oracle as O
     n, m = d.get_dimension()
@@ -80,7 +86,8 @@ def step_term_scales(name, d, ctl, s, xr, g, gabs, ou, oc, integ="euler"):
     eps = float(ctl.epsilon)
     # u_j = clip(-1/2 sum_k Rinv_jj f2_kj g_k + uf_j), g = dV/dx: sums that cancel (acrobot: network terms ~1e5 for |u| <= 25), so the float32
     # forward error is a few ulps of the sum of the MAGNITUDES of the terms, and the result lives in [umin, umax]
-    S_u = umax[None, :] + 0.5 * np.einsum("jj,bkj,bk->bj", np.abs(Rinv), np.abs(f2), gabs)
+    # a dense Rinv adds the terms of the other controls' columns (a separate, exactly zero summand when Rinv is diagonal)
+    S_u = umax[None, :] + 0.5 * np.einsum("jj,bkj,bk->bj", np.abs(Rinv), np.abs(f2), gabs) + 0.5 * np.einsum("jq,bkq,bk->bj", _offdiag(Rinv), np.abs(f2), gabs)
     # x'_k = wrap(x_k + dt (f1_k + sum_j f2_kj u_j)): own terms |x_k| + dt |f1_k| [+ pi for an angle: the wrap is (th + pi) mod 2 pi - pi],
     # plus what the control error contributes through dt |f2_kj|.  RK4: the stage derivatives are averaged with weights (1, 2, 2, 1) / 6; their
     # magnitudes are those of stage 1 to first order in dt, which is all a weighting needs
@@ -89,17 +96,23 @@ def step_term_scales(name, d, ctl, s, xr, g, gabs, ou, oc, integ="euler"):
     if integ == "rk4":
         xd1 = O.dynamics_step(s, xr, ou)
         S_x += dt * np.abs(xd1)
-    # cost = dt (e'Qe + du'R du): non-negative terms for the diagonal Q, R of these configs, so relative accuracy holds except for what
-    # the control error contributes: d cost = 2 dt |R du| du_err; + dt (one cost unit x dt)
+    # cost = dt (e'Qe + du'R du): the diagonal terms are non-negative, so relative accuracy holds for them except for what the control error
+    # contributes: d cost = 2 dt |R du| du_err; + dt (one cost unit x dt).  The off-diagonal terms e_i Q_ij e_j and du_i R_ij du_j may cancel:
+    # their magnitudes are added (exactly zero for diagonal Q, R)
     du = ou - np.asarray(ctl.uf, np.float64)[None, :]
-    S_c = 2 * dt * np.einsum("bj,bj->b", np.abs(du @ R.T), S_u) + dt
+    l_off = np.einsum("bi,ij,bj->b", np.abs(du), _offdiag(R), np.abs(du))
+    Q = getattr(ctl, "Q", None)
+    if Q is not None and np.any(_offdiag(np.asarray(Q, np.float64).reshape(n, n))):
+        e = np.abs(O.wrap(s, xr - np.asarray(ctl.xf, np.float64)[None, :]))
+        l_off = l_off + np.einsum("bi,ij,bj->b", e, _offdiag(np.asarray(Q, np.float64).reshape(n, n)), e)
+    S_c = 2 * dt * np.einsum("bj,bj->b", np.abs(du @ R.T), S_u) + dt + dt * l_off
     # residual r = gradV . xdot / (l + eps) + 1: gradV . xdot cancels (it is ~ -l near the optimum): own terms sum_k |g_k xdot_k| / (l + eps),
     # plus the control error through |(f2' g)_j| / (l + eps) and through l itself
     xd = O.dynamics_step(s, xr, ou)
     l = oc / dt
     f2tg = np.abs(np.einsum("bkj,bk->bj", f2, g))
     vdot_abs = np.abs((g * xd).sum(1))
-    dl = 2 * np.einsum("bj,bj->b", np.abs(du @ R.T), S_u)
+    dl = 2 * np.einsum("bj,bj->b", np.abs(du @ R.T), S_u) + l_off
     S_r = (1.0 + (gabs * np.abs(xd)).sum(1) / (l + eps)) + (np.einsum("bj,bj->b", f2tg, S_u) + vdot_abs * dl / (l + eps)) / (l + eps)
     return dict(x_next=S_x, u=S_u, cost=S_c, residual=S_r)
 
