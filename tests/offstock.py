@@ -65,6 +65,13 @@ R_DENSE = {
     3: [[1.5, 0.5, -0.25], [0.5, 1.0, 0.375], [-0.25, 0.375, 0.75]],
 }
 EPSILON = 1e-10
+# configurations registered under a name of their own (tests/linear_shapes.py) -> the built-in system they are an instance of: the class, the
+# stock controller config and the angle list (none for a linear system) are looked up under that name; conftest knows the five built-ins only
+KIND = {}
+
+
+def kind(name):
+    return KIND.get(name, name)
 
 
 def normalization(n):
@@ -108,8 +115,12 @@ def make_offstock_dynamics(name, **override):
     from q_learning_with_hjb_amd.dynamics.quadrotors import NearHoverQuadcopter, Quadrotors2D
     cls, cfg = {"linear": (LinearDynamics, D.linear_dynamics_config), "cartpole": (Cartpole, D.cartpole_dynamics_config),
                 "acrobot": (Acrobot, D.acrobot_dynamics_config), "quad2d": (Quadrotors2D, D.quadrotors2d_dynamics_config),
-                "nearhover": (NearHoverQuadcopter, D.near_hover_dynamics_config)}[name]
-    return cls(cfg(**dynamics_kwargs(name, **override)))
+                "nearhover": (NearHoverQuadcopter, D.near_hover_dynamics_config)}[kind(name)]
+    kw = dynamics_kwargs(name, **override)
+    if name in KIND:                                         # the stock start box has the stock dimension
+        kw.setdefault("x0_mean", list(XF[name]))
+        kw.setdefault("x0_std", [0.5 * (hi - lo) for lo, hi in zip(*OBS[name])])
+    return cls(cfg(**kw))
 
 
 def task_kwargs(name):
@@ -125,11 +136,13 @@ def offstock_vhjb_config(name, **kw):
     d = task_kwargs(name)
     xf = d["xf"]
     d.update(interior_states_mean=xf, boundary_states_mean=xf)
+    if name in KIND:                                         # the stock spreads have the stock dimension
+        d.update(interior_states_std=[1.0] * len(xf), boundary_states_std=[1.0] * len(xf))
     d.update(kw)
     if name == "acrobot":    # make_vhjb_config("acrobot") fixes xf and the box itself: the same base (the cart-pole file's hyper-parameters)
         from q_learning_with_hjb_amd.configs.defaults import cartpole_vhjb_config
         return cartpole_vhjb_config(**d)
-    return make_vhjb_config(name, **d)
+    return make_vhjb_config(kind(name), **d)
 
 
 def offstock_task(name, **override):
@@ -158,7 +171,7 @@ def box_states(name, B, seed, spread=1.0, angle_turns=0.0):
     lo = np.asarray(OBS[name][0], np.float64).clip(min=-3.0)
     hi = np.asarray(OBS[name][1], np.float64).clip(max=3.0)
     if angle_turns:
-        lo[ANGLE_IDX[name]], hi[ANGLE_IDX[name]] = -angle_turns * np.pi, angle_turns * np.pi
+        lo[ANGLE_IDX[kind(name)]], hi[ANGLE_IDX[kind(name)]] = -angle_turns * np.pi, angle_turns * np.pi
     u = rng.uniform(size=(B, DIMS[name][0]))
     return np.asarray(XF[name], np.float64) + (lo + u * (hi - lo)) * spread
 
@@ -199,7 +212,7 @@ def product_controller(name, g):
     d = make_offstock_dynamics(name)
     n, m = DIMS[name]
     Q, R = dense_Q(n), dense_R(m)
-    if name == "linear":
+    if kind(name) == "linear":
         from q_learning_with_hjb_amd.controller.lqr import LQR
         return d, LQR(d, Q, R)
     if name == "cartpole":
