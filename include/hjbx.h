@@ -233,7 +233,7 @@ void hjbx_system_destroy(hjbx_system* sys);
  * p[0..n_params-1]; the exact contract is at the top of csrc/hjbx_user_kernels.hpp).  It is compiled at run time (hiprtc, gfx950, the
  * library's own build flags) INTO THE LIBRARY'S OWN STREAMING KERNELS, float32 and float64: the returned handle works with every
  * hjbx_*_f32 / _f64 entry point of the HJBX_DECLARE block below (wrap, affine, dynamics_step, simulate with HJBX_EULER / HJBX_RK4,
- * initial_state, costs, control_from_grad, hjb_residual, vhjb_step, controller and rollout_feedback with HJBX_CTRL_LINEAR_FEEDBACK).
+ * initial_state, costs, control_from_grad, hjb_residual, vhjb_step, controller and rollout_feedback with HJBX_CTRL_LINEAR_FEEDBACK; any other law: hjbx_user_controller_create below).
  * The matrix-core entry points (hjbx_value_grad_f32, hjbx_vhjb_rollout_f32, the two hjbx_softpd_* ones, hjbx_value_loss_grad_f32) return
  * HJBX_EUNSUPPORTED for such a handle unless it asked for them (hjbx_system_enable_matrix_cores below).  Compilation needs no GPU.  HJBX_EINVAL when the source does not compile
  * (hjbx_last_compile_log returns the compiler's messages for the calling thread's last call), HJBX_EUNSUPPORTED when libhiprtc.so
@@ -633,6 +633,57 @@ int hjbx_rollout_minsnap_tracking_f64(const hjbx_system* sys, const hjbx_task* t
                                       const double* coeff, const double* cum_t, const double* end_pt, int S, int64_t n_plans, double t0,
                                       int T_steps, const double* x0, double* traj, double* u_log, double* cost, double* total_cost,
                                       double* x_final, double* x_ref_log, double* u_ref_log, int64_t B, void* stream);
+
+/* User-defined control laws: the OPEN half of the reference's second plugin surface, "anything with get_control_efforts(x)"
+ * (controller/controller_basic.py:1-5), compiled into the closed-loop rollout kernel (controller/vhjb.py:171-193; the four fixed kinds of
+ * hjbx_controller stay what they are).  `law_source` is the text of the law as device code: member functions of
+ *   template <typename T, typename S> struct UserLaw { T q[n_q]; ... };
+ * `control` (required: the RAW control of one state, clipped to [umin, umax] by the library afterwards) and `reached` (optional, has_reached != 0:
+ * the stop test of HJBX_ROLLOUT_STOP_AT_TARGET); the exact contract is at the top of csrc/hjbx_user_controller_kernels.hpp.  It is compiled
+ * at run time (hiprtc, gfx950, the library's own build flags) for the system `sys` -- one of the five built-in systems or a user-defined one,
+ * whose own source is compiled along -- into a code object of its own with six kernels: the law alone and the whole closed loop with
+ * HJBX_EULER / HJBX_RK4, in float32 and float64.  The law reads n_q parameters q (<= HJBX_LAW_MAX_PARAMS, shared by all environments,
+ * replaceable without a recompile), n_w values per environment (<= HJBX_LAW_MAX_ENV_PARAMS, a (B, n_w) buffer per call) and the time of the step.
+ * The controller COPIES what it needs from `sys` (kind, dimensions, parameters, control limits, dt, a user-defined system's source): it holds
+ * no reference to the handle, which may be destroyed first.  One controller may be used from several threads; its module is loaded per
+ * device at the first launch.
+ * hjbx_user_controller_create compiles eagerly and needs no GPU.  HJBX_EINVAL: NULL arguments, n_q or n_w out of range, a law that does
+ * not compile (hjbx_last_compile_log returns the compiler's messages; after a successful create it lists the kernels that need scratch
+ * memory, which are slow, not wrong: scratch is reported, not refused).  HJBX_EUNSUPPORTED: libhiprtc.so is not available, or a
+ * HJBX_SYS_LINEAR handle whose (n, m) has no kernels.
+ * hjbx_user_controller_set_params replaces q (n_q must be the value given at creation).  hjbx_user_controller_code_object copies up to `len`
+ * bytes of the gfx950 ELF into buf (may be NULL) and returns its size.
+ * hjbx_user_controller_eval_*: u (B, m) = clip(control(x, w, t)) for x (B, n); w (B, n_w), NULL if and only if n_w == 0.
+ * hjbx_user_controller_rollout_*: hjbx_rollout_feedback_* with the law in place of the descriptor, the same outputs (any may be NULL), flags,
+ * task and termination rules; the law and `reached` see t_k = t0 + k dt at step k.  Refused with HJBX_EINVAL before any launch: a NULL
+ * controller, B < 0, T_steps < 0, an unknown integrator or flag, NULL or misaligned x0, w NULL with n_w > 0 or misaligned, a misaligned output,
+ * HJBX_ROLLOUT_STOP_AT_TARGET for a law without `reached`, HJBX_ROLLOUT_TERMINATE or a cost output without a task; HJBX_ZOH:
+ * HJBX_EUNSUPPORTED (not built).  B == 0: HJBX_OK, nothing launched. */
+#define HJBX_HAS_USER_CONTROLLER 1 /* the entry points below exist (an addition, nothing else changed) */
+#define HJBX_LAW_MAX_PARAMS 128
+#define HJBX_LAW_MAX_ENV_PARAMS 32
+typedef struct hjbx_user_controller hjbx_user_controller; /* opaque */
+/* (controller/controller_basic.py:1-5: a Controller subclass's __init__, compiled) */
+int hjbx_user_controller_create(const hjbx_system* sys, const char* law_source, const double* q, int n_q, int n_w, int has_reached,
+                                hjbx_user_controller** out);
+/* (controller/controller_basic.py:1-5: the end of the controller object) */
+void hjbx_user_controller_destroy(hjbx_user_controller* ctl);
+/* (controller/controller_basic.py:1-5: assigning the subclass's gains; no recompile) */
+int hjbx_user_controller_set_params(hjbx_user_controller* ctl, const double* q, int n_q);
+/* (controller/controller_basic.py:1-5 compiled; the closed loop controller/vhjb.py:171-193 around it) */
+size_t hjbx_user_controller_code_object(const hjbx_user_controller* ctl, void* buf, size_t len);
+/* (controller/controller_basic.py:1-5: get_control_efforts, float32) */
+int hjbx_user_controller_eval_f32(hjbx_user_controller* ctl, const float* x, const float* w, double t, float* u, int64_t B, void* stream);
+/* (controller/controller_basic.py:1-5: get_control_efforts, float64) */
+int hjbx_user_controller_eval_f64(hjbx_user_controller* ctl, const double* x, const double* w, double t, double* u, int64_t B, void* stream);
+/* (controller/controller_basic.py:1-5 inside the closed loop controller/vhjb.py:171-193, float32) */
+int hjbx_user_controller_rollout_f32(hjbx_user_controller* ctl, const hjbx_task* task, int integrator, uint32_t flags, double t0, int T_steps,
+                                     const float* x0, const float* w, float* traj, float* u_log, float* cost, int32_t* done_step,
+                                     float* total_cost, float* x_final, int64_t B, void* stream);
+/* (controller/controller_basic.py:1-5 inside the closed loop controller/vhjb.py:171-193, float64) */
+int hjbx_user_controller_rollout_f64(hjbx_user_controller* ctl, const hjbx_task* task, int integrator, uint32_t flags, double t0, int T_steps,
+                                     const double* x0, const double* w, double* traj, double* u_log, double* cost, int32_t* done_step,
+                                     double* total_cost, double* x_final, int64_t B, void* stream);
 
 #ifdef __cplusplus
 }

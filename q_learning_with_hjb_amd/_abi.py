@@ -19,6 +19,7 @@ HJBX_MAX_M = 3
 SYS_LINEAR, SYS_CARTPOLE, SYS_ACROBOT, SYS_QUAD2D, SYS_NEARHOVER, SYS_USER = range(6)
 USER_AFFINE, USER_MANIPULATOR = 0, 1
 USER_MAX_PARAMS = 16
+LAW_MAX_PARAMS, LAW_MAX_ENV_PARAMS = 128, 32
 EULER, RK4, ZOH = 0, 1, 2
 RESIDUAL_NORMALISED, RESIDUAL_RAW = 0, 1
 CTRL_LINEAR_FEEDBACK, CTRL_CARTPOLE_ENERGY, CTRL_ACROBOT_ENERGY, CTRL_DI_TIME_OPTIMAL = 0, 1, 2, 3
@@ -63,6 +64,7 @@ _SOURCES = tuple(dict.fromkeys(u[0] for u in _UNITS))
 _HEADERS = ("hjbx_systems.hpp", "hjbx_internal.hpp", "hjbx_host.hpp", "hjbx_mlp_core.hpp", "hjbx_hessian_kernels.hpp", "hjbx_mlp_kernels.hpp", "hjbx_mlp_x3.hpp", "hjbx_mlp_h2.hpp", "hjbx_stream_kernels.hpp",
             "hjbx_minsnap.hpp",
             "hjbx_user_kernels.hpp", "hjbx_user_mlp_kernels.hpp", "hjbx_mlp_host.hpp", "hjbx_train_coop_kernels.hpp", "hjbx_user_train_kernels.hpp", "hjbx_user_hessian_kernels.hpp",
+            "hjbx_user_controller_kernels.hpp",
             "hjbx_adam.hpp", os.path.join("..", "..", "include", "hjbx.h"))
 
 
@@ -264,7 +266,9 @@ EXPORTED_SYMBOLS = (
      "hjbx_replay_append_workspace_bytes", "hjbx_replay_append_f32", "hjbx_replay_append_f64",
      "hjbx_initial_state_philox_f32", "hjbx_initial_state_philox_f64", "hjbx_rollout_cost_stats_f32", "hjbx_rollout_cost_stats_f64",
      "hjbx_activation_probe_f32", "hjbx_value_hessian_f32", "hjbx_softpd_value_hessian_f32",
-     "hjbx_minsnap_reference_f32", "hjbx_minsnap_reference_f64", "hjbx_rollout_minsnap_tracking_f32", "hjbx_rollout_minsnap_tracking_f64"]
+     "hjbx_minsnap_reference_f32", "hjbx_minsnap_reference_f64", "hjbx_rollout_minsnap_tracking_f32", "hjbx_rollout_minsnap_tracking_f64",
+     "hjbx_user_controller_create", "hjbx_user_controller_destroy", "hjbx_user_controller_set_params", "hjbx_user_controller_code_object",
+     "hjbx_user_controller_eval_f32", "hjbx_user_controller_eval_f64", "hjbx_user_controller_rollout_f32", "hjbx_user_controller_rollout_f64"]
     + [f"hjbx_{k}_{s}" for k in _typed_signatures() for s in ("f32", "f64")]
 )
 
@@ -357,6 +361,21 @@ def lib() -> C.CDLL:
             fn = getattr(L, f"hjbx_rollout_minsnap_tracking_{sfx}")   # (sys, task, ctrl, integrator, the plan as above, x0, 7 outputs, B, stream)
             fn.restype = C.c_int
             fn.argtypes = [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _I32, _I64, _DBL, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]
+        L.hjbx_user_controller_create.restype = C.c_int         # (sys, law_source, q, n_q, n_w, has_reached, out)
+        L.hjbx_user_controller_create.argtypes = [_VP, C.c_char_p, _VP, _I32, _I32, _I32, C.POINTER(_VP)]
+        L.hjbx_user_controller_destroy.restype = None
+        L.hjbx_user_controller_destroy.argtypes = [_VP]
+        L.hjbx_user_controller_set_params.restype = C.c_int
+        L.hjbx_user_controller_set_params.argtypes = [_VP, _VP, _I32]
+        L.hjbx_user_controller_code_object.restype = C.c_size_t
+        L.hjbx_user_controller_code_object.argtypes = [_VP, _VP, C.c_size_t]
+        for sfx in ("f32", "f64"):
+            fn = getattr(L, f"hjbx_user_controller_eval_{sfx}")       # (ctl, x, w, t, u, B, stream)
+            fn.restype = C.c_int
+            fn.argtypes = [_VP, _VP, _VP, _DBL, _VP, _I64, _VP]
+            fn = getattr(L, f"hjbx_user_controller_rollout_{sfx}")    # (ctl, task, integrator, flags, t0, T_steps, x0, w, 6 outputs, B, stream)
+            fn.restype = C.c_int
+            fn.argtypes = [_VP, _VP, _I32, _U32, _DBL, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]
         L.hjbx_activation_probe_f32.restype = C.c_int
         L.hjbx_activation_probe_f32.argtypes = [_I32, _VP, _VP, _VP, _I64, _VP]
         for name, sig in _typed_signatures().items():
@@ -497,6 +516,50 @@ class SystemHandle:
         if h and _lib is not None:
             try:
                 _lib.hjbx_system_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+
+class UserControllerHandle:
+    """Owns an hjbx_user_controller*: a user-defined control law compiled for one system (hjbx_user_controller_create; the snippet contract
+    is at the top of csrc/hjbx_user_controller_kernels.hpp).  The library copies what it needs from the system handle.  ValueError with
+    the compiler's log when the law does not compile, NotImplementedError when the library has no kernels for the system."""
+
+    def __init__(self, system: SystemHandle, law_source: str, params=(), n_env_params: int = 0, reached: bool = False):
+        self.n, self.m = system.n, system.m
+        self.params = np.ascontiguousarray(params, np.float64).ravel()
+        self.n_env_params, self.reached = int(n_env_params), bool(reached)
+        h = _VP()
+        rc = lib().hjbx_user_controller_create(system.ptr, str(law_source).encode(), self.params.ctypes.data if self.params.size else None,
+                                               int(self.params.size), self.n_env_params, int(self.reached), C.byref(h))
+        if rc == EINVAL and compile_log():
+            raise ValueError(f"hjbx: {last_error()}\n--- compiler log ---\n{compile_log()}")
+        check(rc)
+        self._h = h
+
+    def set_params(self, params):
+        """hjbx_user_controller_set_params: new values of q[0..n_q), no recompile"""
+        q = np.ascontiguousarray(params, np.float64).ravel()
+        check(lib().hjbx_user_controller_set_params(self._h, q.ctypes.data if q.size else None, int(q.size)))
+        self.params = q
+
+    def code_object(self) -> bytes:
+        """hjbx_user_controller_code_object: the gfx950 ELF with the six hjbx_uc_* kernels of this (system, law) pair"""
+        size = lib().hjbx_user_controller_code_object(self._h, None, 0)
+        buf = C.create_string_buffer(size)
+        lib().hjbx_user_controller_code_object(self._h, buf, size)
+        return buf.raw
+
+    @property
+    def ptr(self):
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            try:
+                _lib.hjbx_user_controller_destroy(h)
             except Exception:
                 pass
             self._h = None

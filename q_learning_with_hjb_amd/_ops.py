@@ -327,6 +327,48 @@ def rollout_feedback(sys, ctrl, x0, T_steps, task=None, integrator=_abi.EULER, t
     return dict(traj=traj, u=ulog, cost=cost, done_step=done_step, total_cost=total, x_final=x_final)
 
 
+def _env_params(ctl, w, x):
+    """the (B, n_w) buffer of a user-defined law's per-environment values, or None for a law that reads none"""
+    if ctl.n_env_params == 0:
+        if w is not None:
+            raise ValueError("this control law reads no per-environment values (device_source(): env_params=0)")
+        return None
+    if w is None:
+        raise ValueError(f"this control law reads {ctl.n_env_params} per-environment values: pass env_params of shape (B, {ctl.n_env_params})")
+    _chk(w, "env_params", (x.shape[0], ctl.n_env_params), x.dtype)
+    return w
+
+
+def user_controller_eval(ctl, x, t=0.0, w=None):
+    """hjbx_user_controller_eval_*: u (B, m) = clip(law(x, w, t)) for a _abi.UserControllerHandle."""
+    B = x.shape[0]
+    _chk(x, "x", (B, ctl.n))
+    w = _env_params(ctl, w, x)
+    u = torch.empty((B, ctl.m), dtype=x.dtype, device=x.device)
+    check(_fn("user_controller_eval", x)(ctl.ptr, _p(x), _p(w), float(t), _p(u), B, _stream()))
+    return u
+
+
+def user_controller_rollout(ctl, x0, T_steps, task=None, integrator=_abi.EULER, terminate=False, log_traj=True, log_u=False,
+                            log_cost=False, stop_at_target=False, t0=0.0, w=None):
+    """rollout_feedback under a user-defined control law (hjbx_user_controller_rollout_*): one kernel launch, the same dict of time-major
+    device tensors.  The law sees the time t0 + k dt at step k and row b of `w` (B, n_w) in environment b."""
+    B = x0.shape[0]
+    _chk(x0, "x0", (B, ctl.n))
+    w = _env_params(ctl, w, x0)
+    dt, dev = x0.dtype, x0.device
+    traj = torch.empty((T_steps + 1, B, ctl.n), dtype=dt, device=dev) if log_traj else None
+    ulog = torch.empty((T_steps, B, ctl.m), dtype=dt, device=dev) if log_u else None
+    cost = torch.empty((T_steps + 1, B), dtype=dt, device=dev) if (log_cost and task is not None) else None
+    total = torch.empty((B,), dtype=dt, device=dev) if task is not None else None
+    done_step = torch.empty((B,), dtype=torch.int32, device=dev)
+    x_final = torch.empty_like(x0)
+    flags = (_abi.ROLLOUT_TERMINATE if terminate else 0) | (_abi.ROLLOUT_STOP_AT_TARGET if stop_at_target else 0)
+    check(_fn("user_controller_rollout", x0)(ctl.ptr, ref(task), int(integrator), flags, float(t0), int(T_steps), _p(x0), _p(w), _p(traj),
+                                             _p(ulog), _p(cost), _p(done_step), _p(total), _p(x_final), B, _stream()))
+    return dict(traj=traj, u=ulog, cost=cost, done_step=done_step, total_cost=total, x_final=x_final)
+
+
 def _chk_plan(coeff, cum_t, end_pt, B):
     """-> (S, n_plans) of a device plan: coeff (n_plans, 2, S, 8), cum_t (n_plans, S + 1) float64, end_pt (n_plans, 2); n_plans in {1, B}"""
     _sfx(coeff)

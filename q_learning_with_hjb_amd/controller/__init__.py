@@ -1,0 +1,1 @@
+from .device_controller import DeviceController  # noqa: F401

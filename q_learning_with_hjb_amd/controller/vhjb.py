@@ -25,6 +25,7 @@ from .. import _abi, _ops
 from ..dynamics.dynamics_basic import Dynamics, _from_device, _to_device
 from ..utils.utils import linearize, solve_continuous_are
 from .controller_basic import Controller
+from .device_controller import DeviceController
 
 
 # ------------------------------------------------------------------------------------------------
@@ -771,8 +772,9 @@ class VHJBController(Controller):
         """Seed the replay buffer with closed loops of a model-based controller instead of the (untrained) learned
         policy -- BASELINE configs[2] "energy-shaping warm-start + vhjb".  New behaviour: the reference has the
         controllers (controller/acrobot_energy_shaping.py:74-121, cartpole_energy_shaping.py:65-110) and the buffer
-        (vhjb.py:62-73, 308) but no code joining them.  `controller` is any DeviceFeedbackController; its rollout runs in
-        the fused hjbx_rollout_feedback kernel under this controller's task with rollout_trajectory's termination
+        (vhjb.py:62-73, 308) but no code joining them.  `controller` is any DeviceFeedbackController (its rollout runs in
+        the fused hjbx_rollout_feedback kernel) or DeviceController (a user-defined law, in its own hjbx_user_controller_rollout
+        kernel), under this controller's task with rollout_trajectory's termination
         rules (observation box, forced terminal tuple at `max_steps`), and every emitted (x, cost, done) tuple is
         appended trajectory by trajectory, exactly as `train` appends its own rollouts.
         Returns dict(records, average_trajectory_cost, average_trajectory_length, done_step)."""
@@ -782,8 +784,11 @@ class VHJBController(Controller):
                 self.dynamics.get_initial_state(batch_size=int(num_of_trajectories))
         x0 = self._dev(np.atleast_2d(x0) if isinstance(x0, np.ndarray) else x0).contiguous()
         B = x0.shape[0]
-        out = _ops.rollout_feedback(self.dynamics.system, controller._descriptor(), x0, T, task=self._task,
-                                    integrator=self.dynamics.integrator, terminate=True, log_traj=True, log_u=False, log_cost=True)
+        if isinstance(controller, DeviceController):     # a user-defined law: the same loop, task, flags and logs in its own kernel
+            out = controller._device_rollout(x0, T, task=self._task, terminate=True, log_traj=True, log_u=False, log_cost=True)
+        else:
+            out = _ops.rollout_feedback(self.dynamics.system, controller._descriptor(), x0, T, task=self._task,
+                                        integrator=self.dynamics.integrator, terminate=True, log_traj=True, log_u=False, log_cost=True)
         if self.device_collection:
             records = self._append_rollout(out)
             total, _, tuples, count = self._cost_stats(out)

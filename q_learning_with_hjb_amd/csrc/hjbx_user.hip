@@ -14,6 +14,10 @@
 // for the user's struct, one kernel per (head, activation), compiled at its first use; hjbx_hessian.hip and hjbx_softpd_hessian.hip hand an
 // enabled user handle over to hjbx_user_value_hessian below.
 //
+// User-defined CONTROL LAWS (controller/controller_basic.py:1-5, the other plugin surface) are compiled the same way, at the end of this file:
+// hjbx_user_controller_create builds one more unit, hjbx_user_controller_kernels.hpp, for one (system, law) pair -- the system built-in or
+// user-defined -- as a code object of its own, owned by the controller handle.
+//
 // hiprtc is opened with dlopen at first use: libhjbx.so has no link-time dependency on it, and a process that never creates a user system
 // never loads it.  Compilation needs no GPU (the CPU test compiles a snippet); modules are loaded per device at the first launch.
 #include <hip/hip_runtime.h>
@@ -51,6 +55,7 @@
     X(hjbx_src_user_train, "hjbx_user_train_kernels.hpp", "hjbx_user_train_kernels.hpp") \
     X(hjbx_src_hessian_kernels, "hjbx_hessian_kernels.hpp", "hjbx_hessian_kernels.hpp") \
     X(hjbx_src_user_hessian, "hjbx_user_hessian_kernels.hpp", "hjbx_user_hessian_kernels.hpp") \
+    X(hjbx_src_user_controller, "hjbx_user_controller_kernels.hpp", "hjbx_user_controller_kernels.hpp") \
     X(hjbx_src_abi, "../../include/hjbx.h", "hjbx.h")
 #if !defined(__HIP_DEVICE_COMPILE__)
 #ifndef HJBX_CSRC_DIR
@@ -152,14 +157,18 @@ struct UserProgram {
 };
 
 // Compile `top` (one #include line) for the user's snippet with the library's own flags + `extra`; name expressions are resolved into
-// out->kernel[].  Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
-int compile_unit(const Rtc& R, const char* who, const char* top, const char* unit_name, const std::string& snippet, int user_kind, int n, int m,
-                 int np, const std::vector<std::string>& extra, const std::vector<const char*>& name_exprs, UserUnit* out) {
+// out->kernel[].  `law` is the second in-memory header, "hjbx_user_law_snippet.hpp": the control law of hjbx_user_controller_kernels.hpp
+// (empty for every other unit; `snippet` is empty for a law on a built-in system).
+// Returns HJBX_OK with out->code filled; otherwise the hiprtc log is in g_compile_log and the error is set.
+int compile_unit(const Rtc& R, const char* who, const char* top, const char* unit_name, const std::string& snippet, const std::string& law,
+                 int user_kind, int n, int m, int np, const std::vector<std::string>& extra, const std::vector<const char*>& name_exprs,
+                 UserUnit* out) {
 #define HJBX_TEXT(sym, file, name) sym,
 #define HJBX_NAME(sym, file, name) name,
-    const char* headers[] = {HJBX_EMBEDDED_HEADERS(HJBX_TEXT) kStubInternal, snippet.c_str(), kStubRuntime, kStubStdint, kStubStddef, kStubStddef,
+    static const char kNone[] = "// (none)\n";   // (hiprtc refuses a header without text)
+    const char* headers[] = {HJBX_EMBEDDED_HEADERS(HJBX_TEXT) kStubInternal, snippet.empty() ? kNone : snippet.c_str(), law.empty() ? kNone : law.c_str(), kStubRuntime, kStubStdint, kStubStddef, kStubStddef,
                              kStubTypeTraits};
-    const char* names[] = {HJBX_EMBEDDED_HEADERS(HJBX_NAME) "hjbx_internal.hpp", "hjbx_user_snippet.hpp", "hip/hip_runtime.h", "stdint.h", "stddef.h",
+    const char* names[] = {HJBX_EMBEDDED_HEADERS(HJBX_NAME) "hjbx_internal.hpp", "hjbx_user_snippet.hpp", "hjbx_user_law_snippet.hpp", "hip/hip_runtime.h", "stdint.h", "stddef.h",
                            "cstddef", "type_traits"};
 #undef HJBX_TEXT
 #undef HJBX_NAME
@@ -232,13 +241,14 @@ long kernel_scratch_bytes(const std::vector<char>& code, const std::string& kern
     return -1;
 }
 
-// Launch `kernel` of `unit`: `grid` workgroups of `block` threads on `stream`; the module is loaded on the current device on first use.
-int launch_unit(UserProgram* u, UserUnit& unit, const char* kernel, unsigned grid, unsigned block, void** args, void* stream, const char* who) {
+// Launch `kernel` of `unit`: `grid` workgroups of `block` threads on `stream`; the module is loaded on the current device on first use
+// (`mu` guards the unit's module / function caches).
+int launch_unit(std::mutex& mu, UserUnit& unit, const char* kernel, unsigned grid, unsigned block, void** args, void* stream, const char* who) {
     const int dev = hjbx_current_device();
     if (dev < 0) return hjbx_set_error(HJBX_ENODEVICE, "%s: no HIP device", who);
     hipFunction_t f = nullptr;
     {
-        std::lock_guard<std::mutex> lock(u->mu);
+        std::lock_guard<std::mutex> lock(mu);
         if (!unit.mod[dev]) {
             const hipError_t e = hipModuleLoadData(&unit.mod[dev], unit.code.data());
             if (e != hipSuccess) { unit.mod[dev] = nullptr; return hjbx_set_error(HJBX_EHIP, "hipModuleLoadData: %s", hipGetErrorString(e)); }
@@ -280,7 +290,7 @@ template <typename MakeSpec> int lazy_unit(UserProgram* u, UserUnit& unit, MakeS
         const UnitSpec spec = make_spec();
         g_compile_log.clear();
         const Rtc& R = rtc();   // (loaded: the handle was created through it)
-        int rc = compile_unit(R, who, spec.top, spec.name, u->source, u->user_kind, u->n, u->m, u->np, spec.flags, spec.kernels, &unit);
+        int rc = compile_unit(R, who, spec.top, spec.name, u->source, std::string(), u->user_kind, u->n, u->m, u->np, spec.flags, spec.kernels, &unit);
         for (size_t k = 0; rc == HJBX_OK && k < spec.kernels.size(); ++k) {
             const long scratch = kernel_scratch_bytes(unit.code, unit.kernel[k]);
             if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, unit.kernel[k].c_str());
@@ -414,8 +424,8 @@ extern "C" int hjbx_system_create_from_source(int user_kind, const char* device_
     UserProgram* u = new (std::nothrow) UserProgram();
     if (!u) return hjbx_set_error(HJBX_EINVAL, "out of host memory");
     u->source = device_source; u->user_kind = user_kind; u->n = n; u->m = m; u->np = n_params > 0 ? n_params : 1;
-    if (int rc = compile_unit(R, "hjbx_system_create_from_source", "#include \"hjbx_user_kernels.hpp\"\n", "hjbx_user_system.hip", u->source, user_kind,
-                              n, m, u->np, {}, {}, &u->stream)) {
+    if (int rc = compile_unit(R, "hjbx_system_create_from_source", "#include \"hjbx_user_kernels.hpp\"\n", "hjbx_user_system.hip", u->source, std::string(),
+                              user_kind, n, m, u->np, {}, {}, &u->stream)) {
         delete u;
         return rc;
     }
@@ -472,7 +482,7 @@ extern "C" size_t hjbx_system_code_object(const hjbx_system* sys, int which, voi
 int hjbx_user_launch(const hjbx_system* s, const char* kernel, unsigned grid, void** args, void* stream) {
     UserProgram* u = static_cast<UserProgram*>(s->user);
     if (!u) return hjbx_set_error(HJBX_EINVAL, "system handle has no user program");
-    return launch_unit(u, u->stream, kernel, grid, 256, args, stream, kernel);
+    return launch_unit(u->mu, u->stream, kernel, grid, 256, args, stream, kernel);
 }
 
 // ---- the matrix-core kernels of an enabled handle --------------------------------------------------------------------------------
@@ -493,7 +503,7 @@ int hjbx_user_value_grad(const hjbx_system* s, const hjbx_net& net, const float*
         MlpHeadPd pd{};
         void* a[] = {&blob, &p, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&x, (void*)&V, (void*)&g, (void*)&B, &ngroups,
                      net.soft ? (void*)&soft : (void*)&pd};
-        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[0].c_str(), (unsigned)grid, kMcBlock, a, stream, who);
+        return launch_unit(static_cast<UserProgram*>(s->user)->mu, *unit, unit->kernel[0].c_str(), (unsigned)grid, kMcBlock, a, stream, who);
     });
 }
 
@@ -516,7 +526,7 @@ int hjbx_user_rollout(const hjbx_system* s, const hjbx_task* task, const hjbx_ne
         MlpHeadPd pd{};
         void* a[] = {&blob, &p, &tk, &lim, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&r.t_first, (void*)&r.n_steps, (void*)&r.T_max, (void*)&r.x,
                      (void*)&r.env_order, &o, (void*)&r.B, &ngroups, &ws, &sched, net.soft ? (void*)&soft : (void*)&pd};
-        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[r.integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
+        return launch_unit(static_cast<UserProgram*>(s->user)->mu, *unit, unit->kernel[r.integrator == HJBX_RK4 ? 2 : 1].c_str(), (unsigned)grid, kMcBlock, a,
                            r.stream, who);
     });
 }
@@ -536,7 +546,7 @@ int hjbx_user_value_hessian(const hjbx_system* s, const hjbx_net& net, const flo
         MlpHeadPd pd{};
         void* a[] = {&blob, &p, (void*)&net.W1, (void*)&net.W2, (void*)&net.W3, (void*)&x, (void*)&H, (void*)&dy, (void*)&B, &ngroups,
                      net.soft ? (void*)&soft : (void*)&pd};
-        return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[0].c_str(), (unsigned)grid, kHessWaves * 64, a, stream, who);
+        return launch_unit(static_cast<UserProgram*>(s->user)->mu, *unit, unit->kernel[0].c_str(), (unsigned)grid, kHessWaves * 64, a, stream, who);
     });
 }
 
@@ -550,5 +560,181 @@ int hjbx_user_train_launch(const hjbx_system* s, int activation, int mode, int p
     if (mode < 0 || mode > 1 || (psplit != 1 && psplit != 4)) return hjbx_set_error(HJBX_EINVAL, "%s: residual mode %d / psplit %d", who, mode, psplit);
     UserUnit* unit = nullptr;
     if (int rc = train_unit(s, activation, who, &unit)) return rc;
-    return launch_unit(static_cast<UserProgram*>(s->user), *unit, unit->kernel[2 * mode + (psplit == 4 ? 1 : 0)].c_str(), grid, 256, args, stream, who);
+    return launch_unit(static_cast<UserProgram*>(s->user)->mu, *unit, unit->kernel[2 * mode + (psplit == 4 ? 1 : 0)].c_str(), grid, 256, args, stream, who);
+}
+
+// ---- user-defined control laws (hjbx_user_controller_*, include/hjbx.h) -----------------------------------------------------------
+// The reference's second plugin surface (controller/controller_basic.py:1-5) in the closed loop of controller/vhjb.py:171-193: one code
+// object per (system, law) pair, hjbx_user_controller_kernels.hpp compiled around the law's snippet -- and around the system's own snippet
+// when the system is user-defined.  The controller COPIES what it needs from the system handle (kind, dimensions, parameters, limits, dt,
+// the system's snippet and its -D values): it shares nothing with the handle and outlives it.
+struct hjbx_user_controller {
+    hjbx_system sys;                    // a copy of the handle's plain data; `user` is NULL here
+    std::string sys_source;             // HJBX_SYS_USER: the system's snippet
+    int user_kind = 0, np = 1;
+    std::mutex mu;                      // guards the unit's module / function caches and q
+    UserUnit unit;
+    double q[HJBX_LAW_MAX_PARAMS];
+    int n_q = 0, n_w = 0, has_reached = 0;
+};
+
+namespace {
+#define HJBX_UC_REQUIRE(cond, ...)                                    \
+    do {                                                              \
+        if (!(cond)) return hjbx_set_error(HJBX_EINVAL, __VA_ARGS__); \
+    } while (0)
+
+const char* const kLawKernels[2][3] = {{"hjbx_uc_control_f32", "hjbx_uc_rollout_i0_f32", "hjbx_uc_rollout_i1_f32"},
+                                       {"hjbx_uc_control_f64", "hjbx_uc_rollout_i0_f64", "hjbx_uc_rollout_i1_f64"}};
+
+// the law's parameters as the kernels take them: UserLaw<T, S> is `struct { T q[NQ]; }`
+template <typename T> struct LawBlob { T q[HJBX_LAW_MAX_PARAMS]; };
+template <typename T> LawBlob<T> law_blob(hjbx_user_controller* c) {
+    LawBlob<T> b;
+    std::lock_guard<std::mutex> lock(c->mu);
+    for (int i = 0; i < HJBX_LAW_MAX_PARAMS; ++i) b.q[i] = i < c->n_q ? (T)c->q[i] : T(0);
+    return b;
+}
+template <typename S> const void* system_arg(const S& s) {
+    if constexpr (is_user<S>::value) return &s.blob;
+    else return &s;
+}
+
+template <typename T>
+int user_controller_eval(hjbx_user_controller* c, const T* x, const T* w, double t, T* u, int64_t B, void* stream) {
+    const char* who = "hjbx_user_controller_eval";
+    HJBX_UC_REQUIRE(c != nullptr, "%s: controller handle is NULL", who);
+    HJBX_UC_REQUIRE(B >= 0, "%s: negative batch size %lld", who, (long long)B);
+    if (B == 0) return HJBX_OK;
+    const hjbx_system* s = &c->sys;
+    HJBX_UC_REQUIRE(x != nullptr && aligned_rows(x, (size_t)s->n * sizeof(T)), "%s: x must be a non-NULL device pointer aligned to its row vector width", who);
+    HJBX_UC_REQUIRE(u != nullptr && aligned_rows(u, (size_t)s->m * sizeof(T)), "%s: u must be a non-NULL device pointer aligned to its row vector width", who);
+    HJBX_UC_REQUIRE(c->n_w == 0 || (w != nullptr && aligned_rows(w, (size_t)c->n_w * sizeof(T))),
+                    "%s: this law reads %d per-environment values: w must be a non-NULL (B, %d) device pointer aligned to its row vector width", who, c->n_w, c->n_w);
+    return with_any_system<T>(s, [&](auto S) -> int {
+        using SS = decltype(S);
+        auto law = law_blob<T>(c);
+        auto lim = make_limits<T, SS::M>(s);
+        T tt = (T)t;
+        void* a[] = {const_cast<void*>(system_arg(S)), &law, &lim, &tt, (void*)&x, (void*)&w, (void*)&u, (void*)&B};
+        return launch_unit(c->mu, c->unit, kLawKernels[sizeof(T) == 8][0], (unsigned)((B + 255) / 256), 256, a, stream, who);
+    });
+}
+
+// every argument check of hjbx_rollout_feedback_* (rollout_feedback_impl, hjbx_kernels.hip), before any launch
+template <typename T>
+int user_controller_rollout(hjbx_user_controller* c, const hjbx_task* task, int integ, uint32_t flags, double t0, int T_steps, const T* x0,
+                            const T* w, T* traj, T* u_log, T* cost, int32_t* done_step, T* total_cost, T* x_final, int64_t B, void* stream) {
+    const char* who = "hjbx_user_controller_rollout";
+    HJBX_UC_REQUIRE(c != nullptr, "%s: controller handle is NULL", who);
+    HJBX_UC_REQUIRE(B >= 0, "%s: negative batch size %lld", who, (long long)B);
+    if (B == 0) return HJBX_OK;
+    const hjbx_system* s = &c->sys;
+    if (integ == HJBX_ZOH) return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: HJBX_ZOH stepping is not built for user-defined control laws (HJBX_EULER or HJBX_RK4)", who);
+    HJBX_UC_REQUIRE(integ == HJBX_EULER || integ == HJBX_RK4, "%s: unknown integrator %d", who, integ);
+    HJBX_UC_REQUIRE(T_steps >= 0, "%s: negative horizon", who);
+    HJBX_UC_REQUIRE((flags & ~(HJBX_ROLLOUT_TERMINATE | HJBX_ROLLOUT_STOP_AT_TARGET)) == 0, "%s: unknown rollout flags 0x%x", who, flags);
+    HJBX_UC_REQUIRE(task || !(flags & HJBX_ROLLOUT_TERMINATE), "%s: HJBX_ROLLOUT_TERMINATE needs a task", who);
+    if (task) { if (int rc = check_task(task)) return rc; }
+    HJBX_UC_REQUIRE(task || (!cost && !total_cost), "%s: cost outputs need a task", who);
+    HJBX_UC_REQUIRE(c->has_reached || !(flags & HJBX_ROLLOUT_STOP_AT_TARGET), "%s: HJBX_ROLLOUT_STOP_AT_TARGET needs a law that defines `reached`", who);
+    HJBX_UC_REQUIRE(x0 != nullptr && aligned_rows(x0, (size_t)s->n * sizeof(T)), "%s: x0 must be a non-NULL device pointer aligned to its row vector width", who);
+    HJBX_UC_REQUIRE(c->n_w == 0 || (w != nullptr && aligned_rows(w, (size_t)c->n_w * sizeof(T))),
+                    "%s: this law reads %d per-environment values: w must be a non-NULL (B, %d) device pointer aligned to its row vector width", who, c->n_w, c->n_w);
+    HJBX_UC_REQUIRE(!traj || aligned_rows(traj, (size_t)s->n * sizeof(T)), "%s: traj must be aligned to its row vector width", who);
+    HJBX_UC_REQUIRE(!u_log || aligned_rows(u_log, (size_t)s->m * sizeof(T)), "%s: u_log must be aligned to its row vector width", who);
+    HJBX_UC_REQUIRE(!x_final || aligned_rows(x_final, (size_t)s->n * sizeof(T)), "%s: x_final must be aligned to its row vector width", who);
+    return with_any_system<T>(s, [&](auto S) -> int {
+        using SS = decltype(S);
+        auto law = law_blob<T>(c);
+        auto tk = make_task<T, SS::N, SS::M>(task);
+        auto lim = make_limits<T, SS::M>(s);
+        int has_task = task != nullptr;
+        T tt = (T)t0;
+        void* a[] = {const_cast<void*>(system_arg(S)), &law, &tk, &lim, &flags, &has_task, &T_steps, &tt, (void*)&x0, (void*)&w, (void*)&traj, (void*)&u_log,
+                     (void*)&cost, (void*)&done_step, (void*)&total_cost, (void*)&x_final, (void*)&B};
+        return launch_unit(c->mu, c->unit, kLawKernels[sizeof(T) == 8][integ == HJBX_RK4 ? 2 : 1], (unsigned)((B + 255) / 256), 256, a, stream, who);
+    });
+}
+}  // namespace
+
+extern "C" int hjbx_user_controller_create(const hjbx_system* sys, const char* law_source, const double* q, int n_q, int n_w, int has_reached,
+                                           hjbx_user_controller** out) {
+    const char* who = "hjbx_user_controller_create";
+    if (!out) return hjbx_set_error(HJBX_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    g_compile_log.clear();
+    HJBX_UC_REQUIRE(sys != nullptr && law_source != nullptr, "%s: sys / law_source must be non-NULL", who);
+    HJBX_UC_REQUIRE(n_q >= 0 && n_q <= HJBX_LAW_MAX_PARAMS && (n_q == 0 || q), "%s: a control law takes 0..%d parameters, got %d", who, HJBX_LAW_MAX_PARAMS, n_q);
+    HJBX_UC_REQUIRE(n_w >= 0 && n_w <= HJBX_LAW_MAX_ENV_PARAMS, "%s: a control law takes 0..%d per-environment values, got %d", who, HJBX_LAW_MAX_ENV_PARAMS, n_w);
+    HJBX_UC_REQUIRE(sys->kind >= HJBX_SYS_LINEAR && sys->kind <= HJBX_SYS_USER, "%s: unknown system kind %d", who, sys->kind);
+    const UserProgram* up = sys->kind == HJBX_SYS_USER ? static_cast<const UserProgram*>(sys->user) : nullptr;
+    if (sys->kind == HJBX_SYS_USER) {
+        HJBX_UC_REQUIRE(up != nullptr, "%s: system handle has no user program", who);
+    } else if (!with_system<float>(sys, [](auto) {})) {
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: no kernel for system kind %d with n=%d m=%d", who, sys->kind, sys->n, sys->m);
+    }
+    const Rtc& R = rtc();
+    if (!R.ok) {
+        const char* why = dlerror();
+        return hjbx_set_error(HJBX_EUNSUPPORTED, "%s: libhiprtc.so could not be loaded (%s)", who, why ? why : "symbols missing");
+    }
+    hjbx_user_controller* c = new (std::nothrow) hjbx_user_controller();
+    if (!c) return hjbx_set_error(HJBX_EINVAL, "out of host memory");
+    c->sys = *sys;
+    c->sys.user = nullptr;
+    if (up) { c->sys_source = up->source; c->user_kind = up->user_kind; c->np = up->np; }
+    for (int i = 0; i < HJBX_LAW_MAX_PARAMS; ++i) c->q[i] = i < n_q ? q[i] : 0.0;
+    c->n_q = n_q; c->n_w = n_w; c->has_reached = has_reached ? 1 : 0;
+    const std::vector<std::string> flags = {"-DHJBX_LAW_SYSTEM=" + std::to_string(sys->kind), "-DHJBX_LAW_NQ=" + std::to_string(n_q > 0 ? n_q : 1),
+                                            "-DHJBX_LAW_NW=" + std::to_string(n_w), "-DHJBX_LAW_HAS_REACHED=" + std::to_string(c->has_reached)};
+    int rc = compile_unit(R, who, "#include \"hjbx_user_controller_kernels.hpp\"\n", "hjbx_user_controller.hip", c->sys_source, law_source, c->user_kind,
+                          sys->n, sys->m, c->np, flags, {}, &c->unit);
+    // scratch is reported, not refused: a streaming kernel that spills is slow, not wrong
+    for (int p = 0; rc == HJBX_OK && p < 2; ++p)
+        for (int k = 0; rc == HJBX_OK && k < 3; ++k) {
+            const long scratch = kernel_scratch_bytes(c->unit.code, kLawKernels[p][k]);
+            if (scratch < 0) rc = hjbx_set_error(HJBX_EHIP, "%s: kernel %s is missing from the compiled code object", who, kLawKernels[p][k]);
+            else if (scratch > 0) g_compile_log += "note: " + std::string(kLawKernels[p][k]) + " needs " + std::to_string(scratch) + " bytes of scratch per lane\n";
+        }
+    if (rc != HJBX_OK) { delete c; return rc; }
+    *out = c;
+    return HJBX_OK;
+}
+
+extern "C" void hjbx_user_controller_destroy(hjbx_user_controller* c) {
+    if (!c) return;
+    unload_unit(c->unit);
+    delete c;
+}
+
+extern "C" int hjbx_user_controller_set_params(hjbx_user_controller* c, const double* q, int n_q) {
+    HJBX_UC_REQUIRE(c != nullptr, "hjbx_user_controller_set_params: controller handle is NULL");
+    HJBX_UC_REQUIRE(n_q == c->n_q && (n_q == 0 || q), "hjbx_user_controller_set_params: this law was compiled for %d parameters, got %d", c->n_q, n_q);
+    std::lock_guard<std::mutex> lock(c->mu);
+    for (int i = 0; i < n_q; ++i) c->q[i] = q[i];
+    return HJBX_OK;
+}
+
+extern "C" size_t hjbx_user_controller_code_object(const hjbx_user_controller* c, void* buf, size_t len) {
+    if (!c) { hjbx_set_error(HJBX_EINVAL, "hjbx_user_controller_code_object: controller handle is NULL"); return 0; }
+    if (buf && len) memcpy(buf, c->unit.code.data(), len < c->unit.code.size() ? len : c->unit.code.size());
+    return c->unit.code.size();
+}
+
+extern "C" int hjbx_user_controller_eval_f32(hjbx_user_controller* c, const float* x, const float* w, double t, float* u, int64_t B, void* stream) {
+    return user_controller_eval<float>(c, x, w, t, u, B, stream);
+}
+extern "C" int hjbx_user_controller_eval_f64(hjbx_user_controller* c, const double* x, const double* w, double t, double* u, int64_t B, void* stream) {
+    return user_controller_eval<double>(c, x, w, t, u, B, stream);
+}
+extern "C" int hjbx_user_controller_rollout_f32(hjbx_user_controller* c, const hjbx_task* task, int integrator, uint32_t flags, double t0, int T_steps,
+                                                const float* x0, const float* w, float* traj, float* u_log, float* cost, int32_t* done_step,
+                                                float* total_cost, float* x_final, int64_t B, void* stream) {
+    return user_controller_rollout<float>(c, task, integrator, flags, t0, T_steps, x0, w, traj, u_log, cost, done_step, total_cost, x_final, B, stream);
+}
+extern "C" int hjbx_user_controller_rollout_f64(hjbx_user_controller* c, const hjbx_task* task, int integrator, uint32_t flags, double t0, int T_steps,
+                                                const double* x0, const double* w, double* traj, double* u_log, double* cost, int32_t* done_step,
+                                                double* total_cost, double* x_final, int64_t B, void* stream) {
+    return user_controller_rollout<double>(c, task, integrator, flags, t0, T_steps, x0, w, traj, u_log, cost, done_step, total_cost, x_final, B, stream);
 }

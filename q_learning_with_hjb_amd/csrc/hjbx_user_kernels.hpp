@@ -168,7 +168,9 @@ using namespace hjbx;
                                                   x_final, B);                                                                             \
     }
 
-#ifndef HJBX_USER_MATRIX_CORE_UNIT   // the matrix-core unit (hjbx_user_mlp_kernels.hpp) takes UserSystem only: the streaming kernels exist already
+// the matrix-core units (hjbx_user_mlp_kernels.hpp, ...) and the control-law unit (hjbx_user_controller_kernels.hpp) take UserSystem only: the
+// streaming kernels exist already
+#if !defined(HJBX_USER_MATRIX_CORE_UNIT) && !defined(HJBX_USER_CONTROLLER_UNIT)
 HJBX_U_KERNELS(float, f32)
 HJBX_U_KERNELS(double, f64)
 #endif
